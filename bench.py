@@ -7,6 +7,8 @@ the batch shards data-parallel, N x 128 = configs[3] at N=8).
     python bench.py --config 3                       # tol 1e-5 (configs[2])
     python bench.py --config 5                       # 64x64 input, 1024 filters, 3 stacked blocks, 64 images / GPU
     python bench.py --gpus N --steps K --warmup W    # spawns N ranks itself (one process per GPU, RCCL)
+    python bench.py --full                           # ... plus every side measurement listed below
+    python bench.py --dump-outputs DIR               # ... and the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W          # ... or runs as one rank of a launcher
 
@@ -25,6 +27,13 @@ device -- a step with a miss commits nothing, and a timed region that contains o
 measured again (never reported).  `--no-deferred` gives the drop-in behaviour: one
 read-back per solve.
 
+A plain run sets up, warms up, times the K steps and prints the headline line: the
+side measurements below (`fresh_batches`, `dropin`, `other_configs`, `latency_bs1`,
+`roofline`, `cpu_baseline`) run only with `--full`; the `--no-*` switches then drop
+single ones.  `--dump-outputs DIR` writes what the last timed step returned to its
+caller -- logits, loss, evaluation counts -- and the parameters that step's update left,
+as float32 `.npy` files (a fixed, seeded sample of the large tensors, 64 MB at most).
+
 Prints ONE JSON line (rank 0).  `value` = images of all ranks / wall time of exactly
 K steps (barrier + synchronize on both sides, max over ranks); `step_ms` holds the
 per-step median / min / max from HIP events on the compute stream.  A solve that misses
@@ -32,7 +41,7 @@ its enqueued step count costs TIME, not an update: integrate.DeferredLoop keeps 
 batch until its verdict is in and repeats voided batches in order (`config.retries`).
 `fresh_batches` is the same loop on a NEW synthetic batch per step (moving step counts),
 `dropin` the same steps with a read-back per solve (the drop-in odeint / ODEBlock API).
-`other_configs` (default run only) holds short side runs of BASELINE configs 3 and 5 on the same box;
+`other_configs` (`--full` at the default config only) holds short side runs of BASELINE configs 3 and 5 on the same box;
 `latency_bs1` is a side block, not the metric: forward solves of ONE sample of the config's
 state (the reference's bs = 1 NFE census, evaluate.py:97-142), microseconds per evaluation.
 `roofline` is for the dominant kernel -- at the BASELINE configs `k_w4_gemm64h`, the 36
@@ -149,7 +158,7 @@ def build_model(device, cfg, method):
     return model.to(device)
 
 
-def train_step(model, opt, x, y, reducer=None):
+def train_step(model, opt, x, y, reducer=None, keep=None):
     # train.py:40-58.  `cross_entropy` is the package's F.cross_entropy (one launch forward; its backward launch also
     # carries the classifier's Linear layer: csrc/kernels_loss.hip); on CPU tensors (cpu_baseline) it IS F.cross_entropy
     from neural_ode_features_amd import cross_entropy
@@ -162,7 +171,37 @@ def train_step(model, opt, x, y, reducer=None):
         reducer.finish()
     opt.step()
     opt.zero_grad()
+    if keep is not None:        # (--dump-outputs: what this step hands its caller)
+        keep.update(logits=p.detach(), loss=loss.detach(), nfe=(nfe_f, nfe_b))
     return loss, nfe_f, nfe_b
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20            # elements kept of a larger tensor: a fixed, seeded sample
+
+
+def dump_outputs(dirname, arrays):
+    """Write every (name, tensor) as DIR/<name>.npy in float32.  A tensor of more than DUMP_SAMPLE elements is written as
+    the sample of its flattened entries at sorted indices drawn by a generator seeded with 0: the same positions in every
+    run of the same arguments.  Returns the bytes written; refuses more than DUMP_BUDGET_BYTES in all."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    out = []
+    for name, t in arrays:
+        a = t.detach().float().cpu().reshape(-1) if torch.is_tensor(t) else torch.tensor(t, dtype=torch.float32).reshape(-1)
+        if a.numel() > DUMP_SAMPLE:
+            idx = torch.randperm(a.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_SAMPLE].sort().values
+            a = a[idx]
+        elif torch.is_tensor(t):
+            a = a.reshape(t.shape)
+        out.append((name, a.numpy().astype(np.float32)))
+    total = sum(a.nbytes for _, a in out)
+    if total > DUMP_BUDGET_BYTES:
+        raise SystemExit('bench.py: --dump-outputs would write %d bytes (limit %d)' % (total, DUMP_BUDGET_BYTES))
+    for name, a in out:
+        np.save(os.path.join(dirname, name + '.npy'), a)
+    return total
 
 
 def cpu_baseline(state_dict, cfg, method, min_seconds=12.0, max_seconds=30.0):
@@ -302,7 +341,7 @@ def other_configs(args):
     number for them measured on the same box.  A child that fails or runs past its time leaves an `error` entry."""
     out = {}
     for config, extra, limit in ((3, ['--steps', '10', '--warmup', '3'], 300), (5, ['--steps', '4', '--warmup', '2', '--no-dropin'], 420)):
-        cmd = [sys.executable, os.path.abspath(__file__), '--config', str(config), '--method', args.method, '--no-cpu-baseline',
+        cmd = [sys.executable, os.path.abspath(__file__), '--config', str(config), '--method', args.method, '--full', '--no-cpu-baseline',
                '--no-fresh', '--no-latency', '--no-other-configs'] + extra
         env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
         try:
@@ -372,6 +411,12 @@ def main():
     ap.add_argument('--filters', type=int, default=None)
     ap.add_argument('--tol', type=float, default=None)
     ap.add_argument('--method', default='dopri5')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline figure, run the side measurements: fresh batches, drop-in region, other configs, '
+                         'bs = 1 latency, roofline (with its rocprofv3 / held-clock child processes) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one computed (logits, loss, evaluation counts, the updated '
+                         'parameters) as DIR/<name>.npy, float32')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--no-pmc', action='store_true', help='skip the two rocprofv3 --pmc child passes (roofline.traffic = null)')
@@ -402,6 +447,9 @@ def main():
                     help='TESTING ONLY: ranks share the devices that exist (rank %% device_count); exercises the N-rank code '
                          'path on a 1-GPU box, the number it prints is not a measurement')
     args = ap.parse_args()
+    if not args.full:           # a plain run does only what the headline figure needs
+        args.no_cpu_baseline = args.no_roofline = args.no_pmc = args.no_dropin = True
+        args.no_other_configs = args.no_latency = args.no_fresh = True
     cfg = dict(CONFIGS[args.config])
     if args.batch is not None:
         cfg['batch'] = args.batch
@@ -498,8 +546,10 @@ def main():
     # the voided batches in order with a read-back per solve (integrate.DeferredLoop).  A miss costs time, never an update.
     deferred = None if args.no_deferred else integrate.Deferred(device)
 
+    last = {} if (args.dump_outputs and rank == 0) else None
+
     def one_step(xx, yy):
-        return train_step(model, opt, xx, yy, reducer)
+        return train_step(model, opt, xx, yy, reducer, keep=last)
 
     loop = integrate.DeferredLoop(deferred, opt, one_step, reducer) if deferred is not None else None
 
@@ -565,6 +615,13 @@ def main():
     region = timed_region(fixed, ev)
     elapsed, nfe_f, nfe_b = region['elapsed'], region['nfe_f'], region['nfe_b']
     per_step = [ev[i].elapsed_time(ev[i + 1]) for i in range(args.steps)]
+    if last is not None:
+        # the last timed step's return values and the parameters its update left (before any side region trains on)
+        if not last:
+            raise SystemExit('bench.py: --dump-outputs needs at least one timed step')
+        dump_outputs(args.dump_outputs, [('logits', last['logits']), ('loss', last['loss']), ('nfe', last['nfe'])] +
+                     [('param.' + k, v) for k, v in model.named_parameters()])
+        last = None
 
     def over_ranks(value, op):
         if world == 1:

@@ -209,6 +209,18 @@ def make_ode2_train(ref):
     print('odenet_ode2_train loss %.5f nfe_f %s nfe_b %s' % (loss, nfe_f, nfe_b))
 
 
+def make_dropin(ref):
+    """What the drop-in test needs of the reference's model.py, as data: the state_dict (keys, order, values) of
+    ``ODENet(3, n_filters=16, adjoint=True, tol=1e-3)`` and the names of the classes its ODE block is made of."""
+    torch.manual_seed(37)
+    net = ref.ODENet(3, n_filters=16, adjoint=True, tol=1e-3)
+    torch.save({'state_dict': net.state_dict(), 'keys': list(net.state_dict().keys()),
+                'odeblock_class': type(net.odeblock).__name__, 'odefunc_class': type(net.odeblock.odefunc).__name__,
+                'odefunc_children': [(n, type(m).__name__) for n, m in net.odeblock.odefunc.named_children()]},
+               os.path.join(HERE, 'odenet_dropin_c16.pt'))
+    print('odenet_dropin_c16', len(net.state_dict()), 'tensors')
+
+
 def make_stem(ref):
     torch.manual_seed(47)
     gen = torch.Generator().manual_seed(47)
@@ -226,6 +238,9 @@ def make_stem(ref):
 
 def main():
     ref = import_reference_model()
+    if 'dropin' in sys.argv[1:]:       # only the fixture that made the drop-in test self-contained
+        make_dropin(ref)
+        return
     if 'cfg1' in sys.argv[1:]:         # only the fixture added in round 5
         make_odenet_e2e(ref, 'odenet_rk4_f64.pt', 'rk4', 1e-3, 1, 64, 28, 4, 1, seed=61)
         return
@@ -254,6 +269,7 @@ def main():
     make_ode2_train(ref)
     make_stem(ref)
     make_odenet_e2e(ref, 'odenet_rk4_f64.pt', 'rk4', 1e-3, 1, 64, 28, 4, 1, seed=61)
+    make_dropin(ref)
 
 
 if __name__ == '__main__':

@@ -171,7 +171,7 @@ def test_bench_one_rank_through_rccl():
 
 @pytest.mark.timeout(900)
 def test_bench_line_carries_the_contract_keys():
-    """`python bench.py` (N = 1): ONE JSON line with the driver's keys, the roofline object of the dominant kernel and
+    """`python bench.py --full` (N = 1): ONE JSON line with the driver's keys, the roofline object of the dominant kernel and
     the CPU baseline; the roofline fraction is a utilisation (<= 1), the algorithmic figure lives under its own key."""
     import json
     import os
@@ -180,7 +180,7 @@ def test_bench_line_carries_the_contract_keys():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK')}
     # (the default line also carries short side runs of configs 3 and 5 -- a minute of child processes; tools/r05_bench_lines.sh has them)
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '6', '--warmup', '3', '--no-other-configs'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '6', '--warmup', '3', '--no-other-configs'],
                        env=env, capture_output=True, text=True, timeout=800)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith('{')]

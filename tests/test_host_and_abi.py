@@ -190,30 +190,41 @@ def test_odeblock_attribute_surface():
     assert net.odeblock.return_last_only is False
 
 
-@pytest.mark.skipif(not os.path.exists('/root/reference/model.py'), reason='reference checkout not present')
-def test_reference_model_py_runs_on_top_of_the_package_unchanged():
-    """Drop-in: alias the package as `torchdiffeq`, import the reference's model.py as is;
-    its ODEBlock then calls OUR odeint with ITS OWN ODEfunc, which is recognised."""
+def test_reference_state_dict_and_foreign_odefunc_run_on_top_of_the_package(golden_dir):
+    """Drop-in, from what tests/golden/odenet_dropin_c16.pt recorded of the reference's model.py (make_golden.py): its
+    `ODENet(3, n_filters=16, adjoint=True)` state_dict -- keys, order, values -- loads into the package's ODENet unchanged;
+    with the package aliased as `torchdiffeq`, the solver a `from torchdiffeq import odeint_adjoint` module gets is OURS, and
+    it recognises an ODEfunc class of another module (oracle.dynamics.OracleODEfunc: the reference's layout, not the
+    package's class) and takes it to our boundary."""
+    import importlib
     import neural_ode_features_amd as nof
     from neural_ode_features_amd import integrate
+    from oracle.dynamics import OracleODEfunc
+    g = torch.load(os.path.join(golden_dir, 'odenet_dropin_c16.pt'), map_location='cpu', weights_only=False)
+    mine = nof.ODENet(3, n_filters=16, adjoint=True, tol=1e-3)
+    assert mine.odeblock.odeint is integrate.odeint_adjoint
+    assert list(mine.state_dict().keys()) == g['keys'] == list(g['state_dict'].keys())
+    mine.load_state_dict(g['state_dict'])
+    for k, v in mine.state_dict().items():
+        assert torch.equal(v, g['state_dict'][k]), k
+    # the reference's ODE block is an `ODEfunc` of these children; the foreign class stands in for it
+    assert g['odeblock_class'] == 'ODEBlock' and g['odefunc_class'] == 'ODEfunc'
+    func = OracleODEfunc(16)
+    assert type(func).__module__ != type(mine.odeblock.odefunc).__module__
+    assert [n for n, _ in g['odefunc_children'] if n != 'relu'] == [n for n, _ in func.named_children()]
+    func.load_state_dict({k[len('odeblock.odefunc.'):]: v for k, v in g['state_dict'].items() if k.startswith('odeblock.odefunc.')})
     saved = sys.modules.get('torchdiffeq')
     sys.modules['torchdiffeq'] = nof
-    sys.path.insert(0, '/root/reference')
     try:
-        sys.modules.pop('model', None)
-        import model as ref_model
-        net = ref_model.ODENet(3, n_filters=16, adjoint=True, tol=1e-3)
-        assert net.odeblock.odeint is integrate.odeint_adjoint
-        rec = integrate.Recognised(net.odeblock.odefunc)       # the reference's own class
+        tdq = importlib.import_module('torchdiffeq')
+        assert tdq.odeint_adjoint is integrate.odeint_adjoint and tdq.odeint is integrate.odeint
+        rec = integrate.Recognised(func)
         assert rec.dim == 16 and rec.groups == 16
-        mine = nof.ODENet(3, n_filters=16, adjoint=True, tol=1e-3)
-        assert list(mine.state_dict().keys()) == list(net.state_dict().keys())
-        mine.load_state_dict(net.state_dict())
         with pytest.raises(RuntimeError, match='no CPU path'):  # reaches our boundary; no GPU here
-            net(torch.randn(2, 3, 32, 32))
+            tdq.odeint_adjoint(func, torch.randn(2, 16, 8, 8), torch.tensor([0.0, 1.0]), rtol=1e-3, atol=1e-3)
+        with pytest.raises(RuntimeError, match='no CPU path'):
+            mine(torch.randn(2, 3, 32, 32))
     finally:
-        sys.path.remove('/root/reference')
-        sys.modules.pop('model', None)
         if saved is not None:
             sys.modules['torchdiffeq'] = saved
         else:

@@ -6,7 +6,7 @@ cd $GRAFT_REPO_ROOT
 O=gpurun_out/evidence
 mkdir -p $O
 R=$GRAFT_REPO_ROOT
-python bench.py > $O/bench_full.json 2> $O/bench_full.err
+python bench.py --full > $O/bench_full.json 2> $O/bench_full.err
 for f in 1 0; do
   NODE_TUNE_W4_F16=$f python bench.py --steps 30 --warmup 8 --no-roofline --no-cpu-baseline --no-other-configs --no-latency 2>/dev/null | tail -1 > $O/bench_cfg2_f16_$f.json
 done
