@@ -1,7 +1,11 @@
 """Shared helpers for the parity tests (tests/ may import oracle/)."""
+import contextlib
 import copy
+import ctypes
+import os
 
 import torch
+import torch.nn.functional as F
 
 from oracle.dynamics import OracleODEfunc, PARAM_ORDER, odefunc_vjp as oracle_vjp
 
@@ -83,3 +87,98 @@ def per_sample_err(a, b):
     a = a.detach().double().cpu()
     b = b.detach().double().cpu()
     return (a - b).abs().flatten(1).amax(dim=1) / (b.abs().max() + 1e-30)
+
+
+_F64_DEVICE = None
+
+
+def _arbiter_device():
+    """Where the fp64 ARBITER leg of the oracle runs.  The oracle is PyTorch code; its fp64 convolutions on the host are what
+    made the full-size arbiter tests the slowest of the suite (211 s for one case).  Where PyTorch-ROCm can run an fp64
+    conv2d / group_norm forward + backward on the device (its own library path: nothing of this package), the arbiter runs
+    there -- the fp32 oracle leg, the reference-equivalent one, always stays on the CPU.  NODE_TEST_ARBITER=cpu forces the host."""
+    global _F64_DEVICE
+    if _F64_DEVICE is None:
+        _F64_DEVICE = 'cpu'
+        if os.environ.get('NODE_TEST_ARBITER', 'auto') != 'cpu':
+            try:
+                gen = torch.Generator().manual_seed(0)
+                x = torch.randn(2, 8, 8, 8, generator=gen, dtype=torch.float64)
+                w = torch.randn(8, 8, 3, 3, generator=gen, dtype=torch.float64)
+                xg, wg = x.cuda().requires_grad_(True), w.cuda().requires_grad_(True)
+                yg = F.group_norm(F.conv2d(xg, wg, padding=1), 4)
+                yg.square().sum().backward()
+                xc, wc = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
+                yc = F.group_norm(F.conv2d(xc, wc, padding=1), 4)
+                yc.square().sum().backward()
+                if float((yg.detach().cpu() - yc.detach()).abs().max()) < 1e-12 and float((wg.grad.cpu() - wc.grad).abs().max()) < 1e-10:
+                    _F64_DEVICE = 'cuda'
+            except Exception as e:     # no fp64 convolution on this PyTorch-ROCm build: the arbiter stays on the host
+                print('fp64 arbiter stays on the CPU:', type(e).__name__, e)
+    return _F64_DEVICE
+
+
+@contextlib.contextmanager
+def tune_env(**kw):
+    """NODE_TUNE_* (or any) environment settings for the calls inside; the library reads them per call."""
+    old = {k: os.environ.get(k) for k in kw}
+    os.environ.update({k: str(v) for k, v in kw.items()})
+    try:
+        yield
+    finally:
+        for k, v in old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+def kink_free_replay(shape, envs, tol=1e-3, seed=53, t_end=1.0):
+    """Kink-free parameters (make_func(kink_free=True): no ReLU mask can flip, so max-norm comparisons are meaningful) under the
+    fp64 ARBITER, modelled on test_gpu_round2._replay_triplet.  Three kinds of solve, all of odeint_adjoint with dopri5:
+      1. a free-running HIP solve under envs[0], recording the accepted step sizes of both directions (record_dt);
+      2. for every settings dict of `envs`, a HIP replay of those steps (forced_dts / forced_dts_bwd) under it and
+         NODE_TUNE_W4_STATS=1;
+      3. the oracle's replay of the same steps in fp64 on _arbiter_device().
+    Returns (free, [replay per env], fp64).  Each is a dict: 'out' (the state at t_end), 'gy' (grad_y0), 'gp' (the ten parameter
+    gradients by name, in the order of named_parameters()); the HIP ones also 'fwd' / 'bwd' (the solves' statistics), 'nfe' (what
+    func.nfe advanced by) and 'pair' (node_w4_pair_stats after the backward solve)."""
+    import neural_ode_features_amd as nof
+    from neural_ode_features_amd import _lib
+    from oracle import torchdiffeq_restated as tdq
+    N, C, H, W = shape
+    f, twin = make_func(C, seed=seed, device='cuda', kink_free=True)
+    gen = torch.Generator().manual_seed(seed + 1)
+    y = torch.randn(N, C, H, W, generator=gen)
+    wgt = torch.randn(2, N, C, H, W, generator=gen) / (C * H * W) ** 0.5
+    t = torch.tensor([0.0, t_end])
+
+    def hip(env, options):
+        for p in f.parameters():
+            p.grad = None
+        nfe0 = f.nfe
+        with tune_env(NODE_TUNE_W4_STATS='1', **env):
+            yh = y.cuda().requires_grad_(True)
+            out = nof.odeint_adjoint(f, yh, t.cuda(), rtol=tol, atol=tol, method='dopri5', options=options)
+            (out * wgt.cuda()).sum().backward()
+            st = (ctypes.c_int32 * 4)()
+            _lib.check(_lib.load().node_w4_pair_stats(st))
+        return dict(out=out[-1].detach().cpu(), gy=yh.grad.cpu(), gp={n: p.grad.cpu() for n, p in f.named_parameters()},
+                    fwd=dict(f.last_forward_stats), bwd=dict(f.last_backward_stats), nfe=f.nfe - nfe0, pair=list(st))
+
+    free = hip(envs[0], {'record_dt': 1024})
+    fs, bs = free['fwd'], free['bwd']
+    fd = [d for d, a in zip(fs['dts'], fs['accepts']) if a]
+    bd = [d for d, a in zip(bs['dts'], bs['accepts']) if a]
+    assert len(fd) == fs['accepted'] and len(bd) == bs['accepted']
+    print(shape, tol, 'free-running HIP: forward', (fs['accepted'], fs['rejected']), 'backward', (bs['accepted'], bs['rejected']))
+    opts = {'forced_dts': fd, 'forced_dts_bwd': bd}
+    reps = [hip(env, dict(opts)) for env in envs]
+    dev = _arbiter_device()
+    tw = copy.deepcopy(twin).to(torch.float64).to(dev)
+    yo = y.to(torch.float64).to(dev).requires_grad_(True)
+    out_o = tdq.odeint_adjoint(tw, yo, t.to(torch.float64).to(dev), rtol=tol, atol=tol, method='dopri5', options=dict(opts))
+    (out_o * wgt.to(torch.float64).to(dev)).sum().backward()
+    f64 = dict(out=out_o[-1].detach().cpu(), gy=yo.grad.cpu(), gp={n: p.grad.cpu() for n, p in tw.named_parameters()})
+    print('  (fp64 arbiter ran on %s)' % dev)
+    return free, reps, f64

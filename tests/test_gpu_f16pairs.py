@@ -113,15 +113,22 @@ def _adjoint(shape, tol, seed, gscale, env):
                 pair=list(st))
 
 
-@pytest.mark.parametrize('shape,tol', [((32, 128, 8, 8), 1e-3), ((128, 256, 8, 8), 1e-3), ((128, 256, 8, 8), 1e-5), ((8, 128, 16, 16), 1e-3)])
+# the cotangent magnitudes are swept where the pairs run k_w4_gemm64h (C = 128) and where they run the long-reduction kernels on
+# 8 x 8 states, k_w4_gemm128h<2> and k_w4_wgrad64h at T = 16 (C = 512; C = 1024 takes the pipeline on 16 x 16 states only, whose
+# triples leg is not reproducible enough for this test's bounds: profiles/r06_nondeterminism.txt)
+_GSCALE_SWEEP = {((32, 128, 8, 8), 1e-3), ((64, 512, 8, 8), 1e-3)}
+
+
+@pytest.mark.parametrize('shape,tol', [((32, 128, 8, 8), 1e-3), ((128, 256, 8, 8), 1e-3), ((128, 256, 8, 8), 1e-5), ((8, 128, 16, 16), 1e-3),
+                                       ((32, 512, 8, 8), 1e-3), ((64, 512, 8, 8), 1e-3)])     # (C = 512: k_w4_gemm128h<2>, k_w4_wgrad64h T = 16)
 @pytest.mark.parametrize('gscale', [1.0, 1e-6, 1e4])
 def test_pair_and_triple_adjoint_solves_agree(shape, tol, gscale):
     """The whole adjoint solve (forward recompute, data gradients, k_w4_wgrad64h) on fp16 pairs against the same solve on bf16
     triples / fp32 MFMA: identical accept / reject histories and evaluation counts, outputs and gradients equal to rounding (kink-free
     parameters: no ReLU mask can flip), for cotangents six orders of magnitude below and four above the usual ones -- the
     cotangent-side scale follows the data."""
-    if gscale != 1.0 and (shape[0] != 32 or tol != 1e-3):
-        pytest.skip('cotangent magnitudes are swept at one shape')
+    if gscale != 1.0 and (shape, tol) not in _GSCALE_SWEEP:
+        pytest.skip('cotangent magnitudes are swept at the shapes of _GSCALE_SWEEP')
     a = _adjoint(shape, tol, 51, gscale, dict(NODE_TUNE_W4_F16='1', NODE_TUNE_W4_STATS='1'))
     b = _adjoint(shape, tol, 51, gscale, dict(NODE_TUNE_W4_F16='0'))
     assert a['pair'][0] == 1 and a['pair'][1] == 0, a['pair']          # pairs were used; no step had to be repeated

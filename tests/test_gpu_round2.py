@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from oracle import torchdiffeq_restated as tdq
 from oracle.dynamics import odefunc_vjp as oracle_vjp
-from tests.helpers import make_func, per_sample_err, rel_err, robust_grad_err
+from tests.helpers import _arbiter_device, make_func, per_sample_err, rel_err, robust_grad_err
 
 pytestmark = pytest.mark.gpu
 
@@ -96,35 +96,6 @@ def test_full_size_free_running_pipeline_vs_oracle_ordinary_parameters(tol):
         assert l2_y < 2e-2 and l2_p < 2e-2 and frac_y < 0.05 and frac_p < 0.05
     else:
         assert l2_y < 0.1 and l2_p < 0.1
-
-
-_F64_DEVICE = None
-
-
-def _arbiter_device():
-    """Where the fp64 ARBITER leg of the oracle runs.  The oracle is PyTorch code; its fp64 convolutions on the host are what
-    made the full-size arbiter tests the slowest of the suite (211 s for one case).  Where PyTorch-ROCm can run an fp64
-    conv2d / group_norm forward + backward on the device (its own library path: nothing of this package), the arbiter runs
-    there -- the fp32 oracle leg, the reference-equivalent one, always stays on the CPU.  NODE_TEST_ARBITER=cpu forces the host."""
-    global _F64_DEVICE
-    if _F64_DEVICE is None:
-        _F64_DEVICE = 'cpu'
-        if os.environ.get('NODE_TEST_ARBITER', 'auto') != 'cpu':
-            try:
-                gen = torch.Generator().manual_seed(0)
-                x = torch.randn(2, 8, 8, 8, generator=gen, dtype=torch.float64)
-                w = torch.randn(8, 8, 3, 3, generator=gen, dtype=torch.float64)
-                xg, wg = x.cuda().requires_grad_(True), w.cuda().requires_grad_(True)
-                yg = F.group_norm(F.conv2d(xg, wg, padding=1), 4)
-                yg.square().sum().backward()
-                xc, wc = x.clone().requires_grad_(True), w.clone().requires_grad_(True)
-                yc = F.group_norm(F.conv2d(xc, wc, padding=1), 4)
-                yc.square().sum().backward()
-                if float((yg.detach().cpu() - yc.detach()).abs().max()) < 1e-12 and float((wg.grad.cpu() - wc.grad).abs().max()) < 1e-10:
-                    _F64_DEVICE = 'cuda'
-            except Exception as e:     # no fp64 convolution on this PyTorch-ROCm build: the arbiter stays on the host
-                print('fp64 arbiter stays on the CPU:', type(e).__name__, e)
-    return _F64_DEVICE
 
 
 def _replay_triplet(shape, tol, seed, t_end, with_f32=True):
