@@ -439,6 +439,24 @@ size_t node_stem_conv_workspace_bytes(const node_conv_geom* g);
 int node_stem_conv(const node_conv_geom* g, int what, const float* x, const float* w, const float* dy, float* result,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* Retrieval evaluation -- `evaluate.py retrieval` of the reference (evaluate.py:308-361).  For every query i, with scores
+ * s_i[j] = q[i] . x[j] and relevance gt_i[j] = (q_labels[i] == x_labels[j]):
+ *   ap[i]   = sklearn average_precision_score(gt_i, s_i): descending scores, equal scores form ONE threshold; a row with no
+ *             relevant item gives 0.0
+ *   ap_k[i] = average_precision_score of the top min(k, nd) items (the reference's AP@k, evaluate.py:343-346): normalised by
+ *             the relevant items inside the window, 0.0 when there are none.  Among equal scores the HIGHER database index
+ *             ranks first (a stable ascending argsort reversed): that decides which items of a tie at the boundary enter.
+ * -0.0 and +0.0 are one score.  q: [nq, d], x: [nd, d], scores: [nq, nd]  (fp32 row-major, device); labels int32 [nq] /
+ * [nd]; ap, ap_k: fp64 [nq] (device).  nd <= 16384 (one row's sort keys in LDS), d >= 1, k >= 1.  Scores on the fp32
+ * matrix pipe, one workgroup per query row for the ranking, sums in fp64 in a fixed order: bit-reproducible.
+ * node_retrieval_workspace_bytes returns 0 (with a message) for a shape it refuses; node_rank_ap needs no workspace
+ * (ws may be NULL). */
+size_t node_retrieval_workspace_bytes(int nq, int nd, int d);
+int node_retrieval_ap(int nq, int nd, int d, const float* q, const float* x, const int32_t* q_labels, const int32_t* x_labels,
+                      int k, double* ap, double* ap_k, void* ws, size_t ws_bytes, void* stream);
+int node_rank_ap(int nq, int nd, const float* scores, const int32_t* q_labels, const int32_t* x_labels, int k, double* ap,
+                 double* ap_k, void* ws, size_t ws_bytes, void* stream);
+
 /* Event-based per-kernel-class timing (off by default; adds two event records
  * per profiled launch).  begin() resets the counters; end() synchronises the
  * recorded events and fills `out`. */

@@ -38,6 +38,7 @@ EXPORTS = [
     'node_head_loss_scratch_bytes', 'node_head_loss_fwd', 'node_head_loss_bwd',
     'node_flat_workspace_bytes', 'node_flat_begin', 'node_flat_stage', 'node_flat_scalar', 'node_flat_initial_step',
     'node_flat_finish_step', 'node_flat_status_read',
+    'node_retrieval_workspace_bytes', 'node_retrieval_ap', 'node_rank_ap',
 ]
 
 
@@ -236,6 +237,12 @@ def load():
     lib.node_flat_finish_step.argtypes = [P(NodeFlatSolve), i32, vp, vp]
     lib.node_flat_status_read.restype = i32
     lib.node_flat_status_read.argtypes = [P(NodeFlatSolve), P(NodeFlatStatus), vp]
+    lib.node_retrieval_workspace_bytes.restype = sz
+    lib.node_retrieval_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.node_retrieval_ap.restype = i32
+    lib.node_retrieval_ap.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.node_rank_ap.restype = i32
+    lib.node_rank_ap.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     ver = lib.node_abi_version()
     if ver != NODE_ABI_VERSION:
         raise RuntimeError('libnode_hip ABI %d != binding ABI %d' % (ver, NODE_ABI_VERSION))

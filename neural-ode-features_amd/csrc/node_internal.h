@@ -510,4 +510,10 @@ void launch_sgd_multi(const SgdTable& tb, int count, size_t max_n, float lr, flo
 void launch_head_bwd(const node_shape& sh, const float* z, const float* gamma, const float* beta, const float* scale,
                      const float* stats, const float* gpool, float* dz, float* gpart, hipStream_t s);
 
+// retrieval evaluation (kernels_retrieval.hip): scores[nq][nd] = q[nq][d] . x[nd][d]^T; per-row AP and AP@k of a score matrix
+constexpr int RET_MAX_ND = 16384;      // one row's sort keys fill 128 KiB of LDS
+void launch_retrieval_scores(const float* q, const float* x, float* scores, int nq, int nd, int d, hipStream_t s);
+void launch_retrieval_rank(const float* scores, int nq, int nd, const int* qlab, const int* xlab, int k, double* ap, double* ap_k,
+                           hipStream_t s);
+
 }  // namespace node

@@ -13,12 +13,17 @@
   accuracy   ONE dense-output solve per batch and tolerance at t1 = [.05, ..., 1] (`return_last_only = False`; the ODE stem of an
              `ode2` run alike, `apply_conv = True`): loss and accuracy of the classifier at EVERY time slice -> `results` (csv)
              with the reference's columns t1, test_loss, test_acc, test_nfe, test_tol (evaluate.py:207-305)
+  retrieval  reads the `features` mode's features.npz: per tolerance slice, per t1 slice, every test image as a query against
+             the test set (database at the last slice 'asym' and at the query's own slice 'sym'), AP and AP@10 on the HIP
+             scoring / ranking kernels (retrieval.py) -> retrieval.csv with the reference's columns ap_asym, ap_sym, ap10_asym,
+             ap10_sym, t1, plus tol (evaluate.py:308-361)
 
 Runs on a run directory written by `neural_ode_features_amd.train` (or any `{'params', 'model'}` checkpoint with the
 reference's state_dict keys).  Test data: `--data file.pt` (`x_test`, `y_test`) or the synthetic set of that run.
 
     python -m neural_ode_features_amd.evaluate features runs_cifar10/odenet --t1 0 0.5 1 --tol 1e-3 1e-1
     python -m neural_ode_features_amd.evaluate nfe runs_cifar10/odenet --limit 100
+    python -m neural_ode_features_amd.evaluate retrieval runs_cifar10/odenet
 """
 from __future__ import annotations
 
@@ -181,9 +186,46 @@ def accuracy(args):
     return out
 
 
+def retrieval(args, k=10):
+    """evaluate.py:308-361: per-query AP and AP@10 of the test set against itself, features of every time slice as queries,
+    on the HIP kernels of `retrieval.average_precision` instead of one sklearn call per query.
+
+    The reference's `features()` writes `[tols, T, N, D]` while its `retrieval()` indexes `[T, N, D]`, so the reference loop
+    runs here once per tolerance slice.  Everything else is kept as written, quirks included: the features are normalised
+    along axis -2 (the SAMPLE axis, not the feature axis) plus 1e-7, on the host in numpy, so that the scores start from
+    bit-for-bit the reference's inputs; 'asym' ranks the database of the last time slice, 'sym' that of the query's own
+    slice (for 'ode' stems, whose slices are 2T, the same indices); every image is a query, and the query itself stays in
+    the database.  -> retrieval.csv with the reference's columns ap_asym, ap_sym, ap10_asym, ap10_sym, t1, plus tol: one
+    row per (tol, t1, query)."""
+    import pandas as pd
+    from .retrieval import average_precision
+    path = os.path.join(args.run, 'features.npz')
+    if not os.path.exists(path):
+        raise SystemExit('no pre-extracted features found: %s (run the `features` mode first)' % path)
+    with np.load(path) as f:
+        feats, y_true, t1s, tols = f['features'], f['y_true'], f['t1s'], f['tols']
+    feats = feats / (np.linalg.norm(feats, axis=-2, keepdims=True) + 1e-7)
+    labels = torch.from_numpy(y_true.astype(np.int32)).to(args.device)
+    frames = []
+    for ti, tol in enumerate(tols):
+        fd = torch.from_numpy(np.ascontiguousarray(feats[ti])).to(args.device)          # [T, N, D]
+        for i, t1 in enumerate(t1s):
+            ap_asym, ap10_asym = average_precision(fd[i], fd[-1], labels, labels, k=k)   # t1 = 1 for the database
+            ap_sym, ap10_sym = average_precision(fd[i], fd[i], labels, labels, k=k)      # the same t1 for queries and database
+            frames.append(pd.DataFrame({'ap_asym': ap_asym.cpu().numpy(), 'ap_sym': ap_sym.cpu().numpy(),
+                                        'ap10_asym': ap10_asym.cpu().numpy(), 'ap10_sym': ap10_sym.cpu().numpy(),
+                                        't1': t1, 'tol': tol}))
+    out = os.path.join(args.run, 'retrieval.csv')
+    df = pd.concat(frames, ignore_index=True)
+    df.to_csv(out, index=False)
+    print(df.groupby(['tol', 't1']).mean())
+    return out
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description='features / nfe / tradeoff / accuracy evaluations of the reference on the HIP backend')
-    ap.add_argument('mode', choices=('features', 'nfe', 'tradeoff', 'accuracy'))
+    ap = argparse.ArgumentParser(description='features / nfe / tradeoff / accuracy / retrieval evaluations of the reference on the HIP '
+                                             'backend')
+    ap.add_argument('mode', choices=('features', 'nfe', 'tradeoff', 'accuracy', 'retrieval'))
     ap.add_argument('run')
     ap.add_argument('--t1', type=float, nargs='+', default=np.arange(0, 1.05, .05).tolist())      # evaluate.py:424
     ap.add_argument('--tol', type=float, nargs='+', default=[1e-3, 1e-2, 1e-1, 1e0, 1e1, 1e2])      # evaluate.py:423
@@ -192,7 +234,7 @@ def main(argv=None):
     if not torch.cuda.is_available():
         raise SystemExit('neural_ode_features_amd.evaluate needs a HIP device: the ODE block has no CPU path')
     args.device = torch.device('cuda')
-    return {'features': features, 'nfe': nfe, 'tradeoff': tradeoff, 'accuracy': accuracy}[args.mode](args)
+    return {'features': features, 'nfe': nfe, 'tradeoff': tradeoff, 'accuracy': accuracy, 'retrieval': retrieval}[args.mode](args)
 
 
 if __name__ == '__main__':
