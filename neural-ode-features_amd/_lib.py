@@ -12,7 +12,7 @@ import os
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, 'csrc', 'libnode_hip.so')
-# Diagnostics build (build.py --diag): the product library plus the timing ablations, in-kernel stamps and the
+# Diagnostics build (build.py --diag): the product library plus the in-kernel stamps and the
 # measured-and-rejected kernel variants.  Only tools/ and the `-m diag` tests ask for it, by NODE_HIP_DIAG=1 in the
 # environment of their own process; nothing in the package does.
 LIB_DIAG_PATH = os.path.join(HERE, 'csrc', 'libnode_hip_diag.so')

@@ -2,8 +2,8 @@
 
     python neural-ode-features_amd/build.py [--force] [--diag]
 
-`--diag` also links libnode_hip_diag.so: the same objects with kernels_w4.hip compiled -DNODE_DIAG, i.e. WITH the timing
-ablations (results wrong by design), the in-kernel stamps and the measured-and-rejected kernel variants that tools/ and the
+`--diag` also links libnode_hip_diag.so: the same objects with DIAG_SOURCES compiled -DNODE_DIAG, i.e. WITH the in-kernel
+stamps and the measured-and-rejected kernel variants (kernels_w4_diag.hip, which no other build compiles) that tools/ and the
 `-m diag` tests use (NODE_HIP_DIAG=1 makes _lib.load() take it).  The product library contains none of them.
 
 hipcc cross-compiles for gfx950 without a GPU; the built .so stays next to the
@@ -19,9 +19,10 @@ CSRC = os.path.join(HERE, 'csrc')
 ROOT = os.path.dirname(HERE)
 LIB = os.path.join(CSRC, 'libnode_hip.so')
 LIB_DIAG = os.path.join(CSRC, 'libnode_hip_diag.so')
-DIAG_SOURCES = ['kernels_w4.hip', 'kernels_tiny_solve.hip']       # translation units that hold `#ifdef NODE_DIAG` code
-SOURCES = ['kernels_layout.hip', 'kernels_pointwise.hip', 'kernels_conv.hip', 'kernels_wgrad.hip', 'kernels_head.hip', 'kernels_loss.hip', 'kernels_optim.hip', 'kernels_w4.hip', 'kernels_w4s.hip', 'kernels_stem.hip', 'kernels_tiny.hip', 'kernels_tiny_solve.hip', 'kernels_retrieval.hip', 'stem_api.hip', 'retrieval_api.hip', 'node_api.hip']
-HEADERS = [os.path.join(CSRC, 'node_internal.h'), os.path.join(CSRC, 'wino4.h'), os.path.join(CSRC, 'stem.h'), os.path.join(CSRC, 'step_control.h'), os.path.join(ROOT, 'include', 'node_hip.h')]
+# translation units that hold `#ifdef NODE_DIAG` code (w4_gemm.h's stamps among it), and one that is not in SOURCES: diagnostics library only
+DIAG_SOURCES = ['kernels_w4_bf16.hip', 'kernels_w4_f16.hip', 'w4_select.hip', 'kernels_w4_diag.hip', 'kernels_tiny_solve.hip']
+SOURCES = ['kernels_layout.hip', 'kernels_pointwise.hip', 'kernels_conv.hip', 'kernels_wgrad.hip', 'kernels_head.hip', 'kernels_loss.hip', 'kernels_optim.hip', 'kernels_w4_pack.hip', 'kernels_w4_f32.hip', 'kernels_w4_bf16.hip', 'kernels_w4_f16.hip', 'kernels_w4_wgrad.hip', 'w4_select.hip', 'kernels_w4s.hip', 'kernels_stem.hip', 'kernels_tiny.hip', 'kernels_tiny_solve.hip', 'kernels_retrieval.hip', 'stem_api.hip', 'retrieval_api.hip', 'node_api.hip']
+HEADERS = [os.path.join(CSRC, 'node_internal.h'), os.path.join(CSRC, 'wino4.h'), os.path.join(CSRC, 'w4_gemm.h'), os.path.join(CSRC, 'stem.h'), os.path.join(CSRC, 'step_control.h'), os.path.join(ROOT, 'include', 'node_hip.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function',
          '-ffp-contract=fast']
@@ -56,7 +57,7 @@ def _link(lib, objs, verbose):
 def build(force=False, verbose=True, diag=False):
     """Compile every HIP translation unit for gfx950 and link libnode_hip.so (and, with `diag`, libnode_hip_diag.so)."""
     if force:
-        for s in SOURCES:
+        for s in SOURCES + [d for d in DIAG_SOURCES if d not in SOURCES]:
             for suffix in ('.o', '.diag.o'):
                 o = os.path.join(CSRC, s.replace('.hip', suffix))
                 if os.path.exists(o):
@@ -75,6 +76,7 @@ def build(force=False, verbose=True, diag=False):
         _link(LIB, objs, verbose)
     if diag:
         dobjs = [_compile(s, diag=True) if s in DIAG_SOURCES else o for s, o in zip(SOURCES, objs)]
+        dobjs += [_compile(s, diag=True) for s in DIAG_SOURCES if s not in SOURCES]
         if _stale(LIB_DIAG, dobjs):
             _link(LIB_DIAG, dobjs, verbose)
     return LIB

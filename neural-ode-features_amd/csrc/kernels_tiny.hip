@@ -9,7 +9,7 @@
 // profiles/r04_latency_bs1_trace.txt); a kernel boundary costs ~1.5 us, and nothing in an evaluation is large.  Here:
 //   * DIRECT convolution (filters 2.4 MB per conv as fp32; 6.9 MB as packed, column-padded bf16 triples) on the bf16 matrix
 //     pipe at fp32 accuracy -- every operand an exact sum of three bf16 parts, six of the nine part products
-//     (v_mfma_f32_16x16x32_bf16, the split of kernels_w4.hip);
+//     (v_mfma_f32_16x16x32_bf16, the split of w4_gemm.h);
 //   * a workgroup = (sample, GroupNorm group, slice of CS input channels): its 16-column MFMA tile holds the group's <= 16
 //     output channels, so the GroupNorm behind the convolution needs nothing from another group;
 //   * the K slices of a group (C / CS workgroups: 4 at C = 256, 8x8) leave their partial sums in a scratch buffer and count
@@ -32,7 +32,7 @@ typedef unsigned t_u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// x = h + m + l exactly (three bf16 parts of an fp32 value), eight values at a time (kernels_w4.hip: w4_split8)
+// x = h + m + l exactly (three bf16 parts of an fp32 value), eight values at a time (w4_gemm.h: w4_split8)
 __device__ __forceinline__ void tiny_split8(const float4& p, const float4& q, t_u32x4& hh, t_u32x4& mm, t_u32x4& ll) {
   const t_f32x2 v[4] = {{p.x, p.y}, {p.z, p.w}, {q.x, q.y}, {q.z, q.w}};
 #pragma unroll

@@ -8,7 +8,7 @@
 //     convolutions' filters -- 2 x 27 KB of exact bf16 triples -- in LDS from the first instruction to the last: after the
 //     prologue no filter byte moves;
 //   * a convolution is: the 32-channel slice of the input block arrives (8 KB), nine K steps of v_mfma_f32_16x16x32_bf16 (six
-//     part products each: fp32 accuracy, the split of kernels_w4.hip), the 64 x 16 partial sums go to the block's REDUCER
+//     part products each: fp32 accuracy, the split of w4_gemm.h), the 64 x 16 partial sums go to the block's REDUCER
 //     (the workgroup with ks == gp mod KS), which adds the slices in slice order, applies bias + t x time map + GroupNorm
 //     (+ ReLU) and publishes the block -- workers of the next convolution wait for exactly the two blocks they read
 //     (point-to-point: no grid barrier anywhere in an evaluation);

@@ -48,7 +48,7 @@ namespace node {
 #endif
 constexpr int W4S_THREADS = W4S_THREADS_DEF;   // two waves = 32 channels of one sample: whole 128-B lines of M, V and the NHWC copies
 
-// V and Z -- written once here, read once by the next GEMM -- leave write-through (see st_wt in kernels_w4.hip)
+// V and Z -- written once here, read once by the next GEMM -- leave write-through (see st_wt in w4_gemm.h)
 #ifndef NODE_WT_STORES
 #define NODE_WT_STORES 1
 #endif

@@ -190,7 +190,7 @@ void launch_w4s_to_nchw(const float* src_w4s, float* dst_nchw, int N, int C, int
 void launch_w4s_tmap(const float* tmap0, const float* tmap1, float* out0, float* out1, int C, int Q, hipStream_t s);
 void launch_w4s_emit_outputs(const Dims& d, const EmitArgs& a, hipStream_t s);
 
-// F(4x4,3x3)-domain weight gradient of both conv layers (k_w4_wgrad, kernels_w4.hip).
+// F(4x4,3x3)-domain weight gradient of both conv layers (k_w4_wgrad, kernels_w4_wgrad.hip).
 //   Z  [comp 36][co/32][sample N][co%32][tile 4]   Z = A dz A^T of the conv output's cotangent: a lane's 16 B are four
 //      rows of the reduction for one output channel; what a wave of the producing pass writes per component is 256
 //      contiguous bytes
@@ -209,11 +209,11 @@ void launch_w4_wgrad(const W4WgradArgs& a, hipStream_t s);
 bool w4_wgrad_f16_fits(int N, int C);
 void launch_w4_wgrad_f16(const unsigned* V1, const unsigned* Z1, const unsigned* V2, const unsigned* Z2, float* dU, const Ctrl* ctrl, int N, int C,
                          const int* v1_exp, const int* v2_exp, const int* z_exp, hipStream_t s);
-void w4_refresh_tuning();     // re-read the NODE_TUNE_W4_* switches (once per C-ABI call; kernels_w4.hip)
+void w4_refresh_tuning();     // re-read the NODE_TUNE_W4_* switches (once per C-ABI call; w4_select.hip)
 __host__ __device__ inline size_t w4_z_elems(int N, int C) { return (size_t)W4_COMPS * 4 * N * C; }
 __host__ __device__ inline size_t w4_du_elems(int C) { return (size_t)2 * W4_COMPS * C * C; }
 
-// launchers (kernels_w4.hip)
+// launchers (kernels_w4_pack.hip, w4_select.hip; w4_gemm.h has the map of the kernel files)
 // smallest rtol / atol of an adaptive solve that takes the pipeline (Solver::choose_w4 has the error budget); a hair under
 // 1e-5 so that a tolerance that went through a float keeps comparing equal
 constexpr float W4_MIN_TOL = 0.99e-5f;
@@ -228,7 +228,7 @@ void launch_w4_pack(const W4PackJobs& jobs, int count, int C, hipStream_t s);
 void launch_w4_gemm(const float* V, const float* U, float* M, const Ctrl* ctrl, int N, int C, hipStream_t s,
                     const unsigned short* Ub = nullptr);
 // fp16-pair operands (V pairs at 2^*v_exp, U pairs at 2^*u_exp): M = the same fp32 products, unscaled in the epilogue
-bool w4_f16_fits(int N, int C);     // N % 16 == 0, C % 64 == 0, NODE_TUNE_W4_F16 != 0
+bool w4_f16_fits(int N, int C);     // NODE_TUNE_W4_F16 != 0 and the selector (w4_select.hip) has an fp16-pair kernel for the batch
 void launch_w4_gemm_f16(const unsigned* Vh, const unsigned* Uh, float* M, const Ctrl* ctrl, int N, int C, const int* v_exp, const int* u_exp,
                         hipStream_t s);
 // diagnostics (node_w4_split3): out[3 i .. 3 i + 2] = the three bf16 parts of x[i] as the GEMM kernels split it; n % 8 == 0

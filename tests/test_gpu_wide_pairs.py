@@ -1,6 +1,6 @@
 """GPU parity of the fp16-PAIR kernels at long reductions (C = 512 and 1024: what configs[4] runs) INSIDE whole adjoint solves,
 against the fp64 oracle.  Pairs run only in adaptive dopri5 solves whose virtual batch Nv (N; 4 N for 16 x 16 states) and width
-pass w4_f16_fits (csrc/kernels_w4.hip): every single-evaluation test at C >= 512 runs the bf16-triple kernels instead, and the
+pass w4_f16_fits (csrc/w4_select.hip): every single-evaluation test at C >= 512 runs the bf16-triple kernels instead, and the
 convolution-only pair tests take their scales from k_w4_scales, not from the GroupNorm passes that set them in a solve.  Here a
 free-running solve supplies the step sizes, and the same steps are replayed on the device and by the fp64 oracle
 (tests.helpers.kink_free_replay): forward pair GEMMs, the cotangent-side exponent, k_w4_wgrad64h at (C / 128)^2 = 16 and 64 tiles

@@ -53,7 +53,7 @@ def test_header_matrices_belong_to_the_points_the_header_names():
 
 
 def test_weight_gradient_identity_in_the_f4x4_domain():
-    """What k_w4_wgrad + k_theta_finalize compute (csrc/kernels_w4.hip): with V = B^T d B the conv's own row operand and
+    """What k_w4_wgrad + k_theta_finalize compute (csrc/kernels_w4_wgrad.hip): with V = B^T d B the conv's own row operand and
     Z = A dz A^T of the output cotangent, dW = G^T (sum over tiles V * Z) G is the weight gradient of the 3x3 correlation
     -- checked in fp64 on an 8x8 image (2x2 tiles with the zero halo the pipeline uses) against the direct sum."""
     text = open(os.path.join(ROOT, 'neural-ode-features_amd', 'csrc', 'wino4.h')).read()

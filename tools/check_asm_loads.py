@@ -1,10 +1,10 @@
 #!/usr/bin/env python
-"""Build-time guard for the two kernels whose operand requests are inline asm with hand-counted waits (k_w4_gemm128b,
-k_w4_wgrad128b; csrc/kernels_w4.hip): the compiler treats an asm load's '=v' destination as defined at the asm statement, so
+"""Build-time guard for the kernels whose operand requests are inline asm with hand-counted waits (k_w4_gemm128b in
+csrc/kernels_w4_bf16.hip, k_w4_wgrad128b in kernels_w4_wgrad.hip, k_w4_gemm128h and k_w4_gemm256h in kernels_w4_f16.hip): the compiler treats an asm load's '=v' destination as defined at the asm statement, so
 correctness relies on it never reading, copying, moving or overwriting that register while the request is in flight.  This
-script compiles kernels_w4.hip to device assembly and walks both kernels instruction by instruction: every
+script compiles those files to device assembly and walks the kernels instruction by instruction: every
 `global_load_dwordx4` opens its destination registers, every `s_waitcnt vmcnt(N)` retires all but the N youngest vector-memory
-operations (the walk is linear in program order -- both kernels are straight-line apart from their
+operations (the walk is linear in program order -- the kernels are straight-line apart from their
 one K loop, whose body begins and ends with nothing in flight), and ANY mention of an open register by another instruction (a use, a v_mov, an overwrite) -- or any scratch
 access -- is reported.  Exit code 1 on a violation.  (Advisor finding, round 3.)
 
@@ -18,6 +18,9 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, 'neural-ode-features_amd', 'csrc')
+ASM_FILES = ('kernels_w4_bf16.hip', 'kernels_w4_wgrad.hip', 'kernels_w4_f16.hip')      # where KERNELS live
+# the files whose asm register loads carry counted waits in separate statements (walked in the assembly); kernels_w4_diag.hip: LDS-DMA pieces
+W4_FILES = ASM_FILES + ('kernels_w4_diag.hip',)
 KERNELS = ('k_w4_gemm128b', 'k_w4_wgrad128b', 'k_w4_gemm128h', 'k_w4_gemm256h')
 LOAD_WAW_OK = ('k_w4_gemm128h',)
 # kernels that may spill OUTSIDE their K loop (k_w4_gemm256h: 256 accumulators leave the AGPRs through a few spilled words at the loop's exit):
@@ -106,11 +109,11 @@ def check_statement_sources():
     """Source-level rules for the OTHER hand-written vector-memory asm of the library (advisor finding, round 5): an asm statement
     that loads into registers must carry its own `s_waitcnt vmcnt(0)` (kernels_tiny_solve.hip: the results cannot be used above the
     wait, and the compiler never sees a request in flight) with EARLY-CLOBBER outputs (`=&v`: an output may not share a register with
-    a pointer input of a later request of the same statement); an asm LDS-DMA piece (`global_load_lds_dwordx4`: kernels_w4.hip) has no
+    a pointer input of a later request of the same statement); an asm LDS-DMA piece (`global_load_lds_dwordx4`: kernels_w4_wgrad.hip, kernels_w4_diag.hip) has no
     register destination at all and must restore M0 in the statement that writes it.  Checked for both the product and the
     diagnostics build: the rules are on the source text."""
     bad = []
-    for fn in ('kernels_tiny_solve.hip', 'kernels_tiny.hip', 'kernels_w4.hip'):
+    for fn in ('kernels_tiny_solve.hip', 'kernels_tiny.hip') + W4_FILES:
         src = open(os.path.join(CSRC, fn)).read()
         for m in re.finditer(r'asm volatile\((.*?)\);', src, re.S):
             st = m.group(1)
@@ -122,8 +125,8 @@ def check_statement_sources():
             loads = len(re.findall(r'global_load_dword|TS_Q\b', st))
             if loads == 0:
                 continue
-            if fn == 'kernels_w4.hip':
-                continue      # (register loads of kernels_w4.hip carry counted waits in separate statements: walked in the assembly above)
+            if fn in W4_FILES:
+                continue      # (their register loads carry counted waits in separate statements: walked in the assembly above)
             if 's_waitcnt vmcnt(0)' not in st:
                 bad.append('%s:%d: asm load without its own s_waitcnt vmcnt(0) in the statement' % (fn, line))
             if re.search(r'"=v"', st):
@@ -144,13 +147,17 @@ def main():
     hipcc, flags = build_flags()
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, 'kw4.s')
-        cmd = [hipcc] + flags + ['-S', '--cuda-device-only', os.path.join(CSRC, 'kernels_w4.hip'), '-o', out]
-        subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+        for fn in ASM_FILES:
+            part = os.path.join(d, fn + '.s')
+            cmd = [hipcc] + flags + ['-S', '--cuda-device-only', os.path.join(CSRC, fn), '-o', part]
+            subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+            with open(out, 'a') as f:
+                f.write(open(part).read())
         bad = check(out)
     bad += check_statement_sources()
     for b in bad:
         print('check_asm_loads:', b)
-    print('check_asm_loads: %s' % ('%d violation(s)' % len(bad) if bad else 'ok (%s; statement rules: kernels_tiny_solve.hip, kernels_tiny.hip, kernels_w4.hip)' % ', '.join(KERNELS)))
+    print('check_asm_loads: %s' % ('%d violation(s)' % len(bad) if bad else 'ok (%s; statement rules: kernels_tiny_solve.hip, kernels_tiny.hip, %s)' % (', '.join(KERNELS), ', '.join(W4_FILES))))
     return 1 if bad else 0
 
 
