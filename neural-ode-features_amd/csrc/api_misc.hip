@@ -1,0 +1,162 @@
+// C ABI of what stands beside the solver: the F(4x4,3x3) diagnostics, GroupNorm + ReLU and the classifier head as
+// stand-alone layers, the SGD step.
+#include "solver.h"     // (g_w4_pair_stats)
+
+#include <cstring>
+
+using namespace node;
+
+extern "C" {
+
+// Diagnostics: one bias-free 3x3 convolution (pad 1) of an [N, C, 8, 8] tensor through the F(4x4,3x3) pipeline with
+// stand-alone transform kernels around the component GEMMs -- what the solver fuses into its GroupNorm passes.
+size_t node_conv3x3_w4_workspace_bytes(const node_shape* shape) {
+  if (!shape) return 0;
+  const size_t numel = (size_t)shape->n * shape->c * shape->h * shape->w;
+  const int nv = (shape->n * (shape->h == 16 ? 4 : 1) + 7) & ~7;
+  return (2 * numel + 2 * w4_v_elems(nv, shape->c) + w4_u_elems(shape->c)) * sizeof(float) +
+         w4_ub_elems(shape->c) * sizeof(unsigned short) + sizeof(W4Scales) + 8 * 256;
+}
+int node_conv3x3_w4(const node_shape* shape, const float* weight, int dgrad, const float* x, float* y, void* ws,
+                    size_t ws_bytes, void* stream) {
+  w4_refresh_tuning();     // (the NODE_TUNE_W4_* switches: once per call, not per launch)
+  if (!shape || !weight || !x || !y || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  Dims d;
+  TRY(dims_for(shape, &d));
+  const bool sq8 = d.H == 8 && d.W == 8, sq16 = d.H == 16 && d.W == 16;
+  if (!((sq8 || sq16) && d.C % 64 == 0 && (d.N * (sq16 ? 4 : 1)) % 8 == 0))
+    return fail(NODE_ERR_UNSUPPORTED, "the F(4x4,3x3) pipeline takes 8x8 (N %% 8 == 0) or 16x16 (N %% 2 == 0) images, C %% 64 == 0");
+  const int Q = sq16 ? 4 : 1, Nv = d.N * Q;
+  if (ws_bytes < node_conv3x3_w4_workspace_bytes(shape)) return fail(NODE_ERR_ARG, "workspace too small");
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  Bump b(ws);
+  float* xn = b.take<float>(d.numel);
+  float* yn = b.take<float>(d.numel);
+  float* V = b.take<float>(w4_v_elems(Nv, d.C));
+  float* M = b.take<float>(w4_v_elems(Nv, d.C));
+  float* U = b.take<float>(w4_u_elems(d.C));
+  unsigned short* Ub = b.take<unsigned short>(w4_ub_elems(d.C));
+  W4Scales* sc = b.take<W4Scales>(1);
+  W4PackJobs jobs;
+  memset(&jobs, 0, sizeof(jobs));
+  const bool b16 = w4_uses_bf16(Nv, d.C);
+  const bool f16 = w4_f16_fits(Nv, d.C);     // fp16-pair operands (k_w4_gemm64h): the scales from max|w| and max|x|
+  if (f16) {
+    (void)hipMemsetAsync(sc, 0, sizeof(W4Scales), st);
+    W4ScaleJobs sj;
+    memset(&sj, 0, sizeof(sj));
+    sj.w[0] = weight; sj.wn = (size_t)d.C * (d.C + 1) * 9; sj.gb[1] = x; sj.vn[0] = d.numel; sj.C = d.C; sj.gn_m = 1; sj.sc = sc;
+    launch_w4_scales(sj, st);
+  }
+  jobs.w[0] = weight; jobs.u[0] = U; jobs.ub[0] = (b16 && !f16) ? Ub : nullptr; jobs.dgrad[0] = dgrad ? 1 : 0;
+  if (f16) { jobs.uh[0] = reinterpret_cast<unsigned*>(U); jobs.uh_exp[0] = &sc->e[W4_E_U1]; }
+  launch_w4_pack(jobs, 1, d.C, st);
+  launch_w4s_from_nchw(x, xn, d.N, d.C, Q, st);
+  launch_w4_input(xn, V, d.N, d.C, Q, Nv, st, f16 ? &sc->e[W4_E_V1] : nullptr);
+  if (f16) launch_w4_gemm_f16(reinterpret_cast<const unsigned*>(V), reinterpret_cast<const unsigned*>(U), M, nullptr, Nv, d.C, &sc->e[W4_E_V1], &sc->e[W4_E_U1], st);
+  else launch_w4_gemm(V, U, M, nullptr, Nv, d.C, st, b16 ? Ub : nullptr);
+  launch_w4_output(M, yn, d.N, d.C, Q, st);
+  launch_w4s_to_nchw(yn, y, d.N, d.C, Q, st);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+int node_w4_pair_stats(int32_t* out4) {
+  if (!out4) return fail(NODE_ERR_NULL, "out4 is NULL");
+  for (int i = 0; i < 4; ++i) out4[i] = g_w4_pair_stats[i];
+  return NODE_OK;
+}
+
+// Diagnostics: the exact three-way bf16 split the component GEMMs apply to their fp32 row operands (k_w4_gemm64b and its
+// siblings), element by element: out[3 i + p] = part p of x[i] as a float.
+int node_w4_split3(const float* x, float* out, size_t n, void* stream) {
+  if (!x || !out) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if (n == 0 || n % 8 != 0) return fail(NODE_ERR_ARG, "n must be a positive multiple of 8");
+  launch_w4_split_check(x, out, n, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+int node_gn_relu_fwd(const node_shape* shape, const float* z, const float* gamma, const float* beta, int relu, float* out,
+                     float* stats, void* stream) {
+  char why[200];
+  const int rc = head_check(shape, why, sizeof(why));
+  if (rc != NODE_OK && rc != NODE_ERR_UNSUPPORTED) return fail(rc, "%s", why);   // (the per-group kernels take any C)
+  if (!z || !gamma || !beta || !out || !stats) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  launch_gn_relu_fwd(*shape, z, gamma, beta, relu, out, stats, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_gn_relu_fwd failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+int node_gn_relu_bwd(const node_shape* shape, const float* z, const float* gamma, const float* beta, const float* stats,
+                     int relu, const float* g_out, float* dz, float* gpart, float* gsum, void* stream) {
+  char why[200];
+  const int rc = head_check(shape, why, sizeof(why));
+  if (rc != NODE_OK && rc != NODE_ERR_UNSUPPORTED) return fail(rc, "%s", why);
+  if (!z || !gamma || !beta || !stats || !g_out || !dz || !gpart) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  launch_gn_relu_bwd(*shape, z, gamma, beta, stats, relu, g_out, dz, gpart, (hipStream_t)stream);
+  if (gsum != nullptr) launch_head_gsum(gpart, gsum, shape->n, shape->c, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_gn_relu_bwd failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+int node_head_fwd(const node_shape* shape, const float* z, const float* gamma, const float* beta, const float* scale,
+                  float* pooled, float* stats, void* stream) {
+  char why[200];
+  const int rc = head_check(shape, why, sizeof(why));
+  if (rc != NODE_OK) return fail(rc, "%s", why);
+  if (!z || !gamma || !beta || !pooled || !stats) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  launch_head_fwd(*shape, z, gamma, beta, scale, pooled, stats, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_head_fwd failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+int node_head_bwd(const node_shape* shape, const float* z, const float* gamma, const float* beta, const float* scale,
+                  const float* stats, const float* g_pooled, float* dz, float* gpart, float* gsum, void* stream) {
+  char why[200];
+  const int rc = head_check(shape, why, sizeof(why));
+  if (rc != NODE_OK) return fail(rc, "%s", why);
+  if (!z || !gamma || !beta || !stats || !g_pooled || !dz || !gpart) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  launch_head_bwd(*shape, z, gamma, beta, scale, stats, g_pooled, dz, gpart, (hipStream_t)stream);
+  if (gsum != nullptr) launch_head_gsum(gpart, gsum, shape->n, shape->c, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_head_bwd failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+int node_sgd_step(const node_sgd_tensor* tensors, int count, float lr, float momentum, float weight_decay, float grad_scale,
+                  const float* skip_if_nonzero, void* stream) {
+  if (count < 0) return fail(NODE_ERR_ARG, "count < 0");
+  if (count == 0) return NODE_OK;
+  if (!tensors) return fail(NODE_ERR_NULL, "tensors is NULL");
+  if (!(lr >= 0.f) || !(momentum >= 0.f) || !(weight_decay >= 0.f)) return fail(NODE_ERR_ARG, "lr / momentum / weight_decay must be >= 0");
+  for (int i = 0; i < count; ++i) {
+    if (!tensors[i].param || !tensors[i].grad) return fail(NODE_ERR_NULL, "tensor %d: a pointer is NULL", i);
+    if (!tensors[i].momentum_buf && momentum != 0.f) return fail(NODE_ERR_NULL, "tensor %d: momentum buffer is NULL with momentum %g", i, momentum);
+    if ((((uintptr_t)tensors[i].param) | ((uintptr_t)tensors[i].grad) | ((uintptr_t)tensors[i].momentum_buf)) & 3)
+      return fail(NODE_ERR_ARG, "tensor %d: pointers must be 4-byte aligned", i);
+  }
+  for (int base = 0; base < count; base += SGD_TABLE) {
+    SgdTable tb;
+    memset(&tb, 0, sizeof(tb));
+    const int m = count - base < SGD_TABLE ? count - base : SGD_TABLE;
+    size_t max_n = 0;
+    for (int i = 0; i < m; ++i) {
+      tb.e[i].p = tensors[base + i].param; tb.e[i].g = tensors[base + i].grad; tb.e[i].m = tensors[base + i].momentum_buf;
+      tb.e[i].n = tensors[base + i].n;
+      if (tb.e[i].n > max_n) max_n = tb.e[i].n;
+    }
+    launch_sgd_multi(tb, m, max_n, lr, momentum, weight_decay, grad_scale, skip_if_nonzero, (hipStream_t)stream);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_sgd_step failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+}  // extern "C"

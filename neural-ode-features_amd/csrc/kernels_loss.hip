@@ -22,7 +22,6 @@
 #include <cstdio>
 
 namespace node {
-int set_error(int code, const char* msg);
 
 namespace {
 

@@ -21,9 +21,9 @@
 //    the MFMAs of unit u and written to the other buffer after them.
 // k_wgrad_p is the geometry-generic fallback (slot table + five VALU per step).
 //
-// The masked column sums of dz (conv-bias, time-channel-weight and d/dt terms) are a
-// separate HBM-bound kernel (k_colsum): inside the GEMM they unbalanced a quarter of
-// the workgroups by 50 %.
+// The masked column sums of dz (conv-bias, time-channel-weight and d/dt terms) are not
+// formed here: inside the GEMM they unbalanced a quarter of the workgroups by 50 %.  The
+// producers of dz form them on the tile they are about to store (masked_colsum_tile).
 #include "node_internal.h"
 #include <cstdlib>
 
@@ -845,90 +845,6 @@ __global__ __launch_bounds__(WG_THREADS) void k_wgrad_p(WgradArgs a, Dims d) {
   wg_store_slab<9>(a, d, g, acc);
   WSTAMP(a.stamps, 4, "s_memtime");
   WSTAMP(a.stamps, 5, "s_memrealtime");
-}
-
-// ============================================================================
-// k_colsum: masked column sums of dz per sample,
-//   spart[n][tap][c] = sum_{pixels p of sample n whose tap neighbour p + tap is inside the image} dz[n, p, c]
-// (the conv-bias gradient is tap 4; t * these are the time-channel weight gradients; their
-// contraction with the time-channel weights is d f / d t).  One workgroup per sample; nine
-// inclusion-exclusion terms from: total, first/last row, first/last column, four corners.
-// ============================================================================
-__global__ __launch_bounds__(256) void k_colsum(const float* __restrict__ dz, float* __restrict__ spart, Dims d) {
-  __shared__ float4 red[9 * 256];      // [pixel group][tap][quad]
-  __shared__ unsigned char flg[256];   // per pixel: bit0 first row, bit1 last row, bit2 first column, bit3 last column
-  const int n = blockIdx.x, tid = threadIdx.x;
-  const int c4n = d.C >> 2;                         // float4 columns
-  const int QB = min(c4n, 256);                     // quads per pass
-  const int ngrp = max(1, min(8, 256 / QB));        // pixel groups working in parallel on one quad
-  for (int p = tid; p < d.HW; p += 256) {
-    const int h = p / d.W, x = p - h * d.W;
-    flg[p] = (unsigned char)((h == 0 ? 1 : 0) | (h == d.H - 1 ? 2 : 0) | (x == 0 ? 4 : 0) | (x == d.W - 1 ? 8 : 0));
-  }
-  __syncthreads();
-  const int ql = tid % QB, pg = tid / QB;
-  const bool active = pg < ngrp;
-  auto add = [](float4& s, const float4& v) { s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w; };
-  auto sub = [](float4& s, const float4& v) { s.x -= v.x; s.y -= v.y; s.z -= v.z; s.w -= v.w; };
-  for (int q0 = 0; q0 < c4n; q0 += QB) {
-    const int q = q0 + ql;
-    const bool on = active && q < c4n;
-    float4 T = make_float4(0.f, 0.f, 0.f, 0.f), rf = T, rl = T, cf = T, cl = T, k00 = T, k01 = T, k10 = T, k11 = T;
-    if (on) {
-      const float* base = dz + (size_t)n * d.HW * d.C + q * 4;
-      for (int p0 = pg; p0 < d.HW; p0 += 4 * ngrp) {
-        float4 v[4];
-        int f[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {   // four independent loads in flight
-          const int p = p0 + i * ngrp;
-          const bool ok = p < d.HW;
-          v[i] = ok ? *reinterpret_cast<const float4*>(base + (size_t)p * d.C) : make_float4(0.f, 0.f, 0.f, 0.f);
-          f[i] = ok ? flg[p] : 0;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          add(T, v[i]);
-          if (f[i] & 1) add(rf, v[i]);
-          if (f[i] & 2) add(rl, v[i]);
-          if (f[i] & 4) add(cf, v[i]);
-          if (f[i] & 8) add(cl, v[i]);
-          if ((f[i] & 5) == 5) add(k00, v[i]);
-          if ((f[i] & 9) == 9) add(k01, v[i]);
-          if ((f[i] & 6) == 6) add(k10, v[i]);
-          if ((f[i] & 10) == 10) add(k11, v[i]);
-        }
-      }
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {   // tap (kh, kw) excludes the first (k == 0) / last (k == 2) row and column
-        const int kh = t / 3, kw = t % 3;
-        float4 o = T;
-        if (kh == 0) sub(o, rf);
-        if (kh == 2) sub(o, rl);
-        if (kw == 0) sub(o, cf);
-        if (kw == 2) sub(o, cl);
-        if (kh == 0 && kw == 0) add(o, k00);
-        if (kh == 0 && kw == 2) add(o, k01);
-        if (kh == 2 && kw == 0) add(o, k10);
-        if (kh == 2 && kw == 2) add(o, k11);
-        red[(pg * 9 + t) * QB + ql] = o;
-      }
-    }
-    __syncthreads();
-    if (on && pg == 0) {
-#pragma unroll
-      for (int t = 0; t < 9; ++t) {
-        float4 o = red[t * QB + ql];
-        for (int r = 1; r < ngrp; ++r) add(o, red[(r * 9 + t) * QB + ql]);
-        *reinterpret_cast<float4*>(spart + ((size_t)n * 9 + t) * d.C + q * 4) = o;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-void launch_colsum(const Dims& d, const float* dz, float* spart, hipStream_t s) {
-  hipLaunchKernelGGL(k_colsum, dim3(d.N), dim3(256), 0, s, dz, spart, d);
 }
 
 // ----------------------------------------------------------------------------

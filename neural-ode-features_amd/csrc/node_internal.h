@@ -198,7 +198,7 @@ void launch_combine_gn(const Dims& d, const CombineGnArgs& a, hipStream_t s);
 // (the conv-bias gradient is tap 4; t x these are the time-channel weight gradients; their contraction with the
 // time-channel weights is d f / d t).  Nine inclusion-exclusion terms from: total, first/last row, first/last
 // column, four corners.  Producers of dz call it on the tile they are about to store, which saves a launch and
-// a pass over dz per layer (k_colsum is what runs otherwise).  `flg[p]`: bit0 first row, bit1 last row, bit2
+// a pass over dz per layer.  `flg[p]`: bit0 first row, bit1 last row, bit2
 // first column, bit3 last column.  Threads = ncols x ngrp (column fastest); `red` holds ngrp * 9 * ncols floats.
 // Call with all threads of the workgroup; contains two barriers.
 __device__ inline void masked_colsum_tile(const float* tile, int ld, int HW, const unsigned char* flg, int ncols,
@@ -421,8 +421,6 @@ struct WgradArgs {
   float* wpart2;
 };
 void launch_wgrad(const Dims& d, const WgradArgs& a, hipStream_t s);
-// masked column sums of dz per sample: spart[N][9][C] (conv-bias / time-channel-weight / d-dt terms)
-void launch_colsum(const Dims& d, const float* dz, float* spart, hipStream_t s);
 size_t wgrad_lds_bytes(const Dims& d);
 
 struct ThetaFinalizeArgs {

@@ -3,10 +3,7 @@
 //
 // node_retrieval_ap runs the queries in chunks of RET_CHUNK rows: scores of the chunk into the workspace, then its ranking.
 // The workspace therefore holds min(nq, RET_CHUNK) x nd scores (<= 256 MiB), whatever the number of queries.
-#include "node_internal.h"
-#include "../../include/node_hip.h"
-#include <cstdarg>
-#include <cstdio>
+#include "host_common.h"
 
 using namespace node;
 
@@ -14,19 +11,10 @@ namespace {
 
 constexpr int RET_CHUNK = 4096;
 
-int failf(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return set_error(code, buf);
-}
-
 int check_sizes(int nq, int nd, int d) {
-  if (nq < 1 || nd < 1 || d < 1) return failf(NODE_ERR_SHAPE, "retrieval shape nq=%d nd=%d d=%d: every size must be >= 1", nq, nd, d);
+  if (nq < 1 || nd < 1 || d < 1) return fail(NODE_ERR_SHAPE, "retrieval shape nq=%d nd=%d d=%d: every size must be >= 1", nq, nd, d);
   if (nd > RET_MAX_ND)
-    return failf(NODE_ERR_UNSUPPORTED, "retrieval database of %d items: at most %d are supported (one row's sort keys in LDS)", nd,
+    return fail(NODE_ERR_UNSUPPORTED, "retrieval database of %d items: at most %d are supported (one row's sort keys in LDS)", nd,
                  RET_MAX_ND);
   return NODE_OK;
 }
@@ -38,13 +26,13 @@ size_t score_bytes(int nq, int nd) {
 
 int launch_ok(const char* what) {
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return failf(NODE_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
   return NODE_OK;
 }
 
 int check_rank_args(const int32_t* q_labels, const int32_t* x_labels, int k, const double* ap, const double* ap_k) {
-  if (!q_labels || !x_labels || !ap || !ap_k) return failf(NODE_ERR_NULL, "a required pointer is NULL");
-  if (k < 1) return failf(NODE_ERR_ARG, "retrieval k=%d: k must be >= 1", k);
+  if (!q_labels || !x_labels || !ap || !ap_k) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if (k < 1) return fail(NODE_ERR_ARG, "retrieval k=%d: k must be >= 1", k);
   return NODE_OK;
 }
 
@@ -61,11 +49,11 @@ int node_retrieval_ap(int nq, int nd, int d, const float* q, const float* x, con
                       int k, double* ap, double* ap_k, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_sizes(nq, nd, d);
   if (rc != NODE_OK) return rc;
-  if (!q || !x || !ws) return failf(NODE_ERR_NULL, "a required pointer is NULL");
+  if (!q || !x || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
   rc = check_rank_args(q_labels, x_labels, k, ap, ap_k);
   if (rc != NODE_OK) return rc;
   if (ws_bytes < score_bytes(nq, nd))
-    return failf(NODE_ERR_WORKSPACE, "retrieval workspace too small: %zu < %zu", ws_bytes, score_bytes(nq, nd));
+    return fail(NODE_ERR_WORKSPACE, "retrieval workspace too small: %zu < %zu", ws_bytes, score_bytes(nq, nd));
   hipStream_t st = (hipStream_t)stream;
   float* scores = (float*)ws;
   for (int q0 = 0; q0 < nq; q0 += RET_CHUNK) {
@@ -84,7 +72,7 @@ int node_rank_ap(int nq, int nd, const float* scores, const int32_t* q_labels, c
   (void)ws_bytes;
   int rc = check_sizes(nq, nd, 1);
   if (rc != NODE_OK) return rc;
-  if (!scores) return failf(NODE_ERR_NULL, "a required pointer is NULL");
+  if (!scores) return fail(NODE_ERR_NULL, "a required pointer is NULL");
   rc = check_rank_args(q_labels, x_labels, k, ap, ap_k);
   if (rc != NODE_OK) return rc;
   launch_retrieval_rank(scores, nq, nd, q_labels, x_labels, k, ap, ap_k, (hipStream_t)stream);

@@ -5,38 +5,14 @@
 //                         conv 3x3/2 | conv 1x1/2 | GN+ReLU | conv 3x3 (+ shortcut) | NHWC -> NCHW
 // backward: NCHW -> NHWC (+ triples) | per convolution: data gradient (+ the shortcut's on top) and weight gradient (the
 //           shortcut's rides in the 3x3's launch) | per GroupNorm: backward pass | ONE reduction launch for every slab
+#include "host_common.h"
 #include "stem.h"
 #include "wino4.h"
-#include "../../include/node_hip.h"
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 
 using namespace node;
 
 namespace {
-
-int failf(int code, const char* fmt, ...) {
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof(buf), fmt, ap);
-  va_end(ap);
-  return set_error(code, buf);
-}
-
-struct Bump {
-  char* base;
-  size_t off;
-  explicit Bump(void* b) : base((char*)b), off(0) {}
-  template <typename T>
-  T* take(size_t count) {
-    off = (off + 255) & ~(size_t)255;
-    T* p = base ? (T*)(base + off) : nullptr;
-    off += count * sizeof(T);
-    return p;
-  }
-};
 
 struct Trip {            // a triples tensor [3][rows + 1][C]
   bf16_t* p;
@@ -200,20 +176,20 @@ StemPlan make_stem_plan(const node_stem_shape* sh, void* base) {
 }
 
 int check_stem_shape(const node_stem_shape* sh) {
-  if (!sh) return failf(NODE_ERR_NULL, "shape is NULL");
-  if (sh->n <= 0 || sh->in_ch <= 0 || sh->h < 5 || sh->w < 5 || sh->filters <= 0) return failf(NODE_ERR_SHAPE, "bad stem shape");
-  if (sh->in_ch > 3) return failf(NODE_ERR_UNSUPPORTED, "the stem's first layer takes in_ch <= 3 (got %d)", sh->in_ch);
-  if (sh->filters % 64 != 0) return failf(NODE_ERR_UNSUPPORTED, "the stem's kernels take filters %% 64 == 0 (got %d)", sh->filters);
+  if (!sh) return fail(NODE_ERR_NULL, "shape is NULL");
+  if (sh->n <= 0 || sh->in_ch <= 0 || sh->h < 5 || sh->w < 5 || sh->filters <= 0) return fail(NODE_ERR_SHAPE, "bad stem shape");
+  if (sh->in_ch > 3) return fail(NODE_ERR_UNSUPPORTED, "the stem's first layer takes in_ch <= 3 (got %d)", sh->in_ch);
+  if (sh->filters % 64 != 0) return fail(NODE_ERR_UNSUPPORTED, "the stem's kernels take filters %% 64 == 0 (got %d)", sh->filters);
   const size_t biggest = (size_t)sh->n * (sh->h - 2) * (sh->w - 2) * 64;
-  if (biggest >= ((size_t)1 << 31)) return failf(NODE_ERR_UNSUPPORTED, "stem tensors must stay under 2^31 elements");
+  if (biggest >= ((size_t)1 << 31)) return fail(NODE_ERR_UNSUPPORTED, "stem tensors must stay under 2^31 elements");
   if (stem_gn_cb((sh->h - 2) * (sh->w - 2), 64, 2) == 0)
-    return failf(NODE_ERR_UNSUPPORTED, "the stem's GroupNorm passes hold (sample, 8 channels) blocks in LDS: images up to %d pixels "
+    return fail(NODE_ERR_UNSUPPORTED, "the stem's GroupNorm passes hold (sample, 8 channels) blocks in LDS: images up to %d pixels "
                  "behind the first layer (got %d x %d)", 150 * 1024 / 64, sh->h - 2, sh->w - 2);
   {   // the last block's GroupNorm passes run on `filters` channels in min(32, filters) groups (model.py:268-271)
     const int cpg = sh->filters / (sh->filters < 32 ? sh->filters : 32);
     const int h1 = (sh->h - 2 - 1) / 2 + 1, w1 = (sh->w - 2 - 1) / 2 + 1, h2 = (h1 - 1) / 2 + 1, w2 = (w1 - 1) / 2 + 1;
     if ((sh->filters & (sh->filters - 1)) != 0 || stem_gn_cb(h2 * w2, sh->filters, cpg) == 0)
-      return failf(NODE_ERR_UNSUPPORTED, "the stem's GroupNorm passes take power-of-two filter counts (whole groups per "
+      return fail(NODE_ERR_UNSUPPORTED, "the stem's GroupNorm passes take power-of-two filter counts (whole groups per "
                    "power-of-two channel block); got %d", sh->filters);
   }
   return NODE_OK;
@@ -303,7 +279,7 @@ SGnArgs gn_args(const float* h, const float* gamma, const float* beta, float* st
 
 int launch_ok(const char* what) {
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return failf(NODE_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
   return NODE_OK;
 }
 
@@ -321,13 +297,13 @@ int node_stem_fwd(const node_stem_shape* shape, const node_stem_params* prm, con
   w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)
   int rc = check_stem_shape(shape);
   if (rc != NODE_OK) return rc;
-  if (!prm || !x || !out || !ws) return failf(NODE_ERR_NULL, "a required pointer is NULL");
+  if (!prm || !x || !out || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
   const float* const* pp = reinterpret_cast<const float* const*>(prm);
   for (int i = 0; i < 16; ++i)
-    if (!pp[i]) return failf(NODE_ERR_NULL, "stem parameter %d is NULL", i);
-  if (((uintptr_t)ws) & 255) return failf(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+    if (!pp[i]) return fail(NODE_ERR_NULL, "stem parameter %d is NULL", i);
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
   StemPlan p = make_stem_plan(shape, ws);
-  if (ws_bytes < p.bytes) return failf(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
+  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
   hipStream_t st = (hipStream_t)stream;
   const int N = p.N, F = p.F;
 
@@ -345,7 +321,7 @@ int node_stem_fwd(const node_stem_shape* shape, const node_stem_params* prm, con
     pa.zero_c[i] = tz[i]->C;
   }
   pa.nzero = 8;
-  if (F > 4096) return failf(NODE_ERR_UNSUPPORTED, "filters > 4096");
+  if (F > 4096) return fail(NODE_ERR_UNSUPPORTED, "filters > 4096");
   launch_stem_prep(pa, st);
   if ((rc = launch_ok("stem_prep")) != NODE_OK) return rc;
 
@@ -424,14 +400,14 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, con
   w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)
   int rc = check_stem_shape(shape);
   if (rc != NODE_OK) return rc;
-  if (!prm || !x || !grad_out || !gr || !ws) return failf(NODE_ERR_NULL, "a required pointer is NULL");
+  if (!prm || !x || !grad_out || !gr || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
   const float* const* pp = reinterpret_cast<const float* const*>(prm);
   float* const* gp = reinterpret_cast<float* const*>(gr);
   for (int i = 0; i < 16; ++i)
-    if (!pp[i] || !gp[i]) return failf(NODE_ERR_NULL, "stem parameter / gradient %d is NULL", i);
-  if (((uintptr_t)ws) & 255) return failf(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+    if (!pp[i] || !gp[i]) return fail(NODE_ERR_NULL, "stem parameter / gradient %d is NULL", i);
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
   StemPlan p = make_stem_plan(shape, ws);
-  if (ws_bytes < p.bytes) return failf(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
+  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
   hipStream_t st = (hipStream_t)stream;
   const int N = p.N, F = p.F;
   const int HW0 = p.H0 * p.W0, HW1 = p.H1 * p.W1, HW2 = p.H2 * p.W2;
@@ -568,11 +544,11 @@ OnePlan make_one(const node_conv_geom* g, void* base) {
   return p;
 }
 int check_geom(const node_conv_geom* g) {
-  if (!g) return failf(NODE_ERR_NULL, "geometry is NULL");
-  if (g->n <= 0 || g->x_h <= 0 || g->x_w <= 0) return failf(NODE_ERR_SHAPE, "bad geometry");
-  if (g->cin % 64 != 0 || g->cout % 64 != 0 || g->cin <= 0 || g->cout <= 0) return failf(NODE_ERR_UNSUPPORTED, "cin, cout must be multiples of 64");
+  if (!g) return fail(NODE_ERR_NULL, "geometry is NULL");
+  if (g->n <= 0 || g->x_h <= 0 || g->x_w <= 0) return fail(NODE_ERR_SHAPE, "bad geometry");
+  if (g->cin % 64 != 0 || g->cout % 64 != 0 || g->cin <= 0 || g->cout <= 0) return fail(NODE_ERR_UNSUPPORTED, "cin, cout must be multiples of 64");
   if (!((g->k == 3 && g->pad == 1) || (g->k == 1 && g->pad == 0)) || (g->stride != 1 && g->stride != 2))
-    return failf(NODE_ERR_UNSUPPORTED, "3x3 pad 1 or 1x1 pad 0, stride 1 or 2");
+    return fail(NODE_ERR_UNSUPPORTED, "3x3 pad 1 or 1x1 pad 0, stride 1 or 2");
   return NODE_OK;
 }
 }  // namespace
@@ -587,10 +563,10 @@ int node_stem_conv(const node_conv_geom* g, int what, const float* x, const floa
   w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)
   int rc = check_geom(g);
   if (rc != NODE_OK) return rc;
-  if (!result || !ws || (what != 1 && !x) || (what != 2 && !w) || (what != 0 && !dy)) return failf(NODE_ERR_NULL, "a required pointer is NULL");
-  if (((uintptr_t)ws) & 255) return failf(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+  if (!result || !ws || (what != 1 && !x) || (what != 2 && !w) || (what != 0 && !dy)) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
   OnePlan p = make_one(g, ws);
-  if (ws_bytes < p.bytes) return failf(NODE_ERR_WORKSPACE, "workspace too small");
+  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "workspace too small");
   hipStream_t st = (hipStream_t)stream;
   const int XHW = g->x_h * g->x_w, YHW = p.YH * p.YW;
   SPrepArgs pa;
@@ -608,7 +584,7 @@ int node_stem_conv(const node_conv_geom* g, int what, const float* x, const floa
     launch_stem_from_nchw(dy, nullptr, p.dyt.p, p.dyt.plane, g->n, g->cout, YHW, st);
     SConvArgs c = conv_dgrad_args(p.dyt, p.f, p.resn, g->n, p.YH, p.YW, g->x_h, g->x_w, g->k, g->stride, g->pad);
     if (g->k == 1 && g->stride == 2) {   // pixels no tap reaches keep a zero gradient
-      if (hipMemsetAsync(p.resn, 0, (size_t)g->n * XHW * g->cin * sizeof(float), st) != hipSuccess) return failf(NODE_ERR_HIP, "memset failed");
+      if (hipMemsetAsync(p.resn, 0, (size_t)g->n * XHW * g->cin * sizeof(float), st) != hipSuccess) return fail(NODE_ERR_HIP, "memset failed");
     }
     launch_stem_conv(c, st);
     launch_stem_to_nchw(p.resn, result, g->n, g->cin, XHW, st);

@@ -1,5 +1,5 @@
 // Winograd F(4x4, 3x3) as a three-stage pipeline (gfx950 only): the 3x3 convolutions of an 8x8 or 16x16 state whose
-// solver tolerance leaves room for the transform's rounding (see Solver::choose_w4, node_api.hip).  A 16x16 image is
+// solver tolerance leaves room for the transform's rounding (see Solver::choose_w4, solver.h).  A 16x16 image is
 // four 8x8 quadrants, each a "virtual sample" of the layouts below (kernels_w4s.hip has the quadrant logic): wherever
 // this file says N or "sample" for V, U, M, Z and the GEMM-side kernels, a 16x16 solve passes 4 N.
 //

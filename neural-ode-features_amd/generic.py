@@ -5,7 +5,7 @@ itself offers dynamics outside the fused path: `--norm batch` (`train.py:202`, `
 not multiples of four, images beyond 32x32.  For a HIP fp32 state those solves run HERE: the caller's `func` is evaluated
 as ordinary PyTorch operations on the current stream, and everything else -- stage states, stage times, the Hairer
 initial step, the mixed error norm per tensor, accept / reject, the next step size, quartic dense output, FSAL -- is
-done on the device by the same controller kernels the fused solves use (`node_flat_*`, csrc/node_api.hip:
+done on the device by the same controller kernels the fused solves use (`node_flat_*`, csrc/api_flat.hip:
 `k_lincomb`, `k_init_norms`, `k_error_norm`, `k_step_controller`, `k_emit_flat`, `k_commit`).  The host takes no
 decision: it enqueues as many steps as the previous solve of the same problem needed and reads the controller back once.
 

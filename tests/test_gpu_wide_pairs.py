@@ -11,7 +11,7 @@ Which kernel a case runs follows from launch_w4_gemm_f16: C >= 512 takes k_w4_ge
 and k_w4_gemm256h + the k_w4_gemm128h<2> tail for components 32..35 where Nv % 64 == 0 and nT2 = (Nv / 64)(C / 256) is a multiple
 of 8 (NODE_TUNE_W4_H256 = 2: wherever Nv % 64 == 0); the weight gradient is k_w4_wgrad64h with T = (C / 128)^2 tiles per component.
 C = 1024 runs the pipeline on 16 x 16 states only: 32 groups of 32 channels fit the quadrant passes, while the 8 x 8 passes hold
-a group in one wave (16 % cpg == 0, csrc/node_api.hip), so an 8 x 8 state at C = 1024 takes the fp32 F(2x2,3x3) kernels and no
+a group in one wave (16 % cpg == 0, csrc/dims.hip), so an 8 x 8 state at C = 1024 takes the fp32 F(2x2,3x3) kernels and no
 pairs.  The tight 8 x 8 claims on k_w4_gemm256h are therefore made at C = 512.
 
 16 x 16 states carry a known defect (profiles/r06_nondeterminism.txt: in < 1 % of solves a few (sample, channel % 16 == 5,

@@ -344,37 +344,6 @@ int main(int argc, char** argv) {
                                   ph[0] / cnt, ph[1] / cnt, ph[2] / cnt, ph[3] / cnt);
 #endif
     }
-    // masked column sums
-    float* sp = dev_zero((size_t)d.N * 9 * C);
-    for (int i = 0; i < 3; ++i) launch_colsum(d, dz, sp, st);
-    CK(hipEventRecord(e0, st));
-    for (int i = 0; i < 10; ++i) launch_colsum(d, dz, sp, st);
-    CK(hipEventRecord(e1, st));
-    CK(hipEventSynchronize(e1));
-    float ms;
-    CK(hipEventElapsedTime(&ms, e0, e1));
-    auto reduce = [&](float* p, size_t per, int nsl) {
-      auto h = to_host(p, (size_t)nsl * per);
-      std::vector<float> r(per, 0.f);
-      for (int s = 0; s < nsl; ++s) for (size_t i = 0; i < per; ++i) r[i] += h[(size_t)s * per + i];
-      return r;
-    };
-    auto hs_ = reduce(sp, 9 * C, d.N);
-    double serr = 0, smax = 0;
-    for (int t = 0; t < 9; ++t)
-      for (int c = 0; c < d.C; ++c) {
-        double acc = 0;
-        for (int n = 0; n < d.N; ++n)
-          for (int h = 0; h < d.H; ++h)
-            for (int x = 0; x < d.W; ++x) {
-              const int hh = h + t / 3 - 1, xx = x + t % 3 - 1;
-              if (hh < 0 || hh >= d.H || xx < 0 || xx >= d.W) continue;
-              acc += (double)hdz[((size_t)n * d.HW + h * d.W + x) * C + c];
-            }
-        serr = std::max(serr, std::fabs(acc - (double)hs_[(size_t)t * C + c]));
-        smax = std::max(smax, std::fabs(acc));
-      }
-    printf("k_colsum %.2f us per launch; vs fp64 host reference: max err %.3e (ref max %.3e)\n", ms * 1e3 / 10, serr, smax);
   } else {
     fprintf(stderr, "unknown bench %s\n", what.c_str());
     return 2;
