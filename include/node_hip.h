@@ -457,6 +457,36 @@ int node_retrieval_ap(int nq, int nd, int d, const float* q, const float* x, con
 int node_rank_ap(int nq, int nd, const float* scores, const int32_t* q_labels, const int32_t* x_labels, int k, double* ap,
                  double* ap_k, void* ws, size_t ws_bytes, void* stream);
 
+/* The input pipeline of the training loop -- the transform chains of utils.py:81-196 -- as ONE launch per batch on a split
+ * that lives in device memory as uint8:
+ *   out[b]        = Normalize(ToTensor(Flip(Jitter(Crop(Pad(data[index[b]]))))))      fp32  [batch, c, h, w]
+ *   out_labels[b] = labels[index[b]]                                                  int64 [batch]
+ * Every stage is switched by a bit of `flags`; with none set the launch is gather + / 255 (the test transform), with
+ * NODE_AUG_NORM alone the normalising test transform.
+ *   NODE_AUG_CROP    RandomCrop(size, padding), zero fill: output pixel (i, j) reads source pixel (i + dy - padding,
+ *                    j + dx - padding), dy and dx uniform on {0 .. 2 padding}, or 0 outside the image
+ *   NODE_AUG_JITTER  ColorJitter(saturation, hue), c == 3 only: fs uniform on [1 - saturation, 1 + saturation], fh uniform on
+ *                    [-hue, hue], in the order a random bit picks; torchvision's tensor formulas in fp32 on [0, 1]
+ *                    (adjust_saturation, adjust_hue), without requantisation to 8 bits between the two
+ *   NODE_AUG_FLIP    RandomHorizontalFlip (p = 0.5)
+ *   NODE_AUG_NORM    (x - mean[ch]) / std[ch]
+ * Random numbers are Philox4x32-10 with key = `seed` (low word, high word) and counter = (dataset index, epoch, call, 0):
+ * what an image looks like depends on (seed, epoch, index[b]) alone, not on the batch, the position in it or the rank.  Call 0
+ * gives w0..w3: dy = (w0 (2 padding + 1)) >> 32, dx likewise from w1, flip = w2 >> 31, hue before saturation = w3 >> 31; call 1:
+ * fs = (1 - saturation) + 2 saturation u(w0), fh = -hue + 2 hue u(w1) with u(w) = (w >> 8) 2^-24, in fp32.
+ * data: uint8 [n, c, h, w]; labels: int64 [n]; index: int64 [batch], all device memory.  An index outside [0, n) reads
+ * nothing: it gives a black image and the label -1.  No workspace, no synchronisation. */
+enum { NODE_AUG_CROP = 1, NODE_AUG_JITTER = 2, NODE_AUG_FLIP = 4, NODE_AUG_NORM = 8 };
+typedef struct node_augment {
+  int32_t n, c, h, w;        /* the split; c is 1 or 3                                                              */
+  int32_t padding;           /* NODE_AUG_CROP: 0 <= 2 padding + 1 <= 65536                                          */
+  uint32_t flags;            /* NODE_AUG_* bits                                                                      */
+  float saturation, hue;     /* NODE_AUG_JITTER: 0 <= saturation <= 1, 0 <= hue <= 0.5                              */
+  float mean[3], std[3];     /* NODE_AUG_NORM: the first c entries, std > 0                                          */
+} node_augment;
+int node_augment_batch(const node_augment* aug, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
+                       uint64_t seed, uint32_t epoch, float* out, int64_t* out_labels, void* stream);
+
 /* Event-based per-kernel-class timing (off by default; adds two event records
  * per profiled launch).  begin() resets the counters; end() synchronises the
  * recorded events and fills `out`. */

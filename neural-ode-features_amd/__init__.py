@@ -10,7 +10,8 @@ reference's `model.py` runs unchanged on top of the HIP library:
 from .integrate import odeint, odeint_adjoint, odefunc_forward, odefunc_vjp  # noqa: F401
 from .modules import ConcatConv2d, ODEBlock, ODEfunc, normalization  # noqa: F401
 from .odenet import FCClassifier, ODEDownsample, ODEDownsample2, ODENet, ResBlock, StackedODENet  # noqa: F401
-from . import dp, graphs, optim, retrieval  # noqa: F401
+from . import augment, dp, graphs, optim, retrieval  # noqa: F401
+from .augment import Augmenter, DeviceSplit  # noqa: F401
 from .optim import FusedSGD  # noqa: F401
 from .head import cross_entropy, linear, linear_cross_entropy  # noqa: F401
 

@@ -39,6 +39,7 @@ EXPORTS = [
     'node_flat_workspace_bytes', 'node_flat_begin', 'node_flat_stage', 'node_flat_scalar', 'node_flat_initial_step',
     'node_flat_finish_step', 'node_flat_status_read',
     'node_retrieval_workspace_bytes', 'node_retrieval_ap', 'node_rank_ap',
+    'node_augment_batch',
 ]
 
 
@@ -133,6 +134,13 @@ class NodeFlatStatus(C.Structure):
 
 
 FLAT_F0, FLAT_PROBE = -1, -2
+
+AUG_CROP, AUG_JITTER, AUG_FLIP, AUG_NORM = 1, 2, 4, 8
+
+
+class NodeAugment(C.Structure):
+    _fields_ = [('n', C.c_int32), ('c', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('padding', C.c_int32),
+                ('flags', C.c_uint32), ('saturation', C.c_float), ('hue', C.c_float), ('mean', C.c_float * 3), ('std', C.c_float * 3)]
 
 
 class NodeHipError(RuntimeError):
@@ -243,6 +251,8 @@ def load():
     lib.node_retrieval_ap.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.node_rank_ap.restype = i32
     lib.node_rank_ap.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.node_augment_batch.restype = i32
+    lib.node_augment_batch.argtypes = [P(NodeAugment), vp, vp, vp, i32, C.c_uint64, C.c_uint32, vp, vp, vp]
     ver = lib.node_abi_version()
     if ver != NODE_ABI_VERSION:
         raise RuntimeError('libnode_hip ABI %d != binding ABI %d' % (ver, NODE_ABI_VERSION))

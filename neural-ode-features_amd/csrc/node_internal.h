@@ -514,4 +514,17 @@ void launch_retrieval_scores(const float* q, const float* x, float* scores, int 
 void launch_retrieval_rank(const float* scores, int nq, int nd, const int* qlab, const int* xlab, int k, double* ap, double* ap_k,
                            hipStream_t s);
 
+// input pipeline (kernels_augment.hip): gather + crop / jitter / flip / normalise of a batch of dataset indices, one launch.
+// The stage bits are the NODE_AUG_* of include/node_hip.h (augment_api.hip asserts that they agree).
+constexpr uint32_t AUG_CROP = 1, AUG_JITTER = 2, AUG_FLIP = 4, AUG_NORM = 8;
+constexpr int AUG_THREADS = 256;
+struct AugmentArgs {
+  int n, h, w, pad;
+  uint32_t flags, epoch, seed_lo, seed_hi;
+  float saturation, hue;
+  float mean[3], std[3];
+};
+void launch_augment(const AugmentArgs& a, int c, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
+                    float* out, int64_t* out_labels, hipStream_t s);
+
 }  // namespace node

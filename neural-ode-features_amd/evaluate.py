@@ -19,7 +19,8 @@
              ap10_sym, t1, plus tol (evaluate.py:308-361)
 
 Runs on a run directory written by `neural_ode_features_amd.train` (or any `{'params', 'model'}` checkpoint with the
-reference's state_dict keys).  Test data: `--data file.pt` (`x_test`, `y_test`) or the synthetic set of that run.
+reference's state_dict keys).  Test data: `--data file.pt` (`x_test`, `y_test`) or the synthetic set of that run; a run
+trained with `--augmentation` gets its test transform (augment.py), a run without the key is taken as `none`.
 
     python -m neural_ode_features_amd.evaluate features runs_cifar10/odenet --t1 0 0.5 1 --tol 1e-3 1e-1
     python -m neural_ode_features_amd.evaluate nfe runs_cifar10/odenet --limit 100
@@ -52,6 +53,18 @@ def load_run(run_dir, which='best'):
         in_ch, out = xte.shape[1], int(blob['y_train'].max()) + 1
     else:
         _, _, xte, yte, in_ch, out = load_data(p)
+    kind = getattr(p, 'augmentation', 'none')        # a run of before the flag has no such key
+    if kind != 'none':
+        # an augmented run trained on the device pipeline's images: the test set goes through its test transform (ToTensor,
+        # plus Normalize for the `...+norm` kinds) and stays on the device
+        if not torch.cuda.is_available():
+            raise SystemExit('neural_ode_features_amd.evaluate needs a HIP device: the input pipeline has no CPU path')
+        if xte.dtype != torch.uint8:
+            raise SystemExit('the run was trained with --augmentation %s: its test images must be uint8 (they are %s)' % (kind, xte.dtype))
+        aug = nof.Augmenter(kind, dataset=p.dataset, seed=p.seed)
+        split = nof.DeviceSplit(xte, yte, torch.device('cuda'))
+        order = torch.arange(len(split), device=split.device)
+        xte = torch.cat([aug.batch(split, order[i:i + 1024], 0, train=False)[0] for i in range(0, len(split), 1024)])
     model = nof.ODENet(in_ch, out=out, n_filters=p.filters, downsample=p.downsample, method=p.method, tol=p.tol,
                        adjoint=p.adjoint, dropout=p.dropout, norm=p.norm)
     model.load_state_dict(ckpt['model'])

@@ -5,12 +5,18 @@ metrics (loss, acc, NFE-F, NFE-B, test_loss, test_acc, test_nfe), same checkpoin
 schedules (`fixed` / `plateau` / `cosine`, train.py:158-163) -- so a run started by the reference continues here and
 the reverse: the model's state_dict keys and the optimizer's state layout are the reference's.
 
-What is NOT here (out of the hot path's scope): torchvision datasets / augmentation and the
-`expman` run-directory bookkeeping.  Data comes from `--data file.pt` (a dict of tensors `x_train, y_train, x_test,
-y_test`) or, by default, a synthetic set of the dataset's shape; the run directory is `--run-dir`.
+What is NOT here (out of the hot path's scope): torchvision datasets and the `expman`
+run-directory bookkeeping.  Data comes from `--data file.pt` (a dict of tensors `x_train, y_train, x_test, y_test`) or, by
+default, a synthetic set of the dataset's shape; the run directory is `--run-dir`.
+
+`--augmentation` (utils.py:81-196: `crop`, `crop+flip+norm`, `crop+jitter+flip+norm`; default `none`) runs the reference's
+transform chains on the device (augment.py): both splits are uploaded once as uint8 (`--data` must then hold uint8 images),
+the epoch's permutation is uploaded once per epoch, and every batch -- gather, crop, jitter, flip, normalise, labels -- is one
+launch of the library, so no host-to-device copy remains inside a step.  The random numbers are counted by (dataset index,
+epoch): a resumed run continues the sequence.  With `none` the host loop below is what it always was.
 
     python -m neural_ode_features_amd.train --dataset cifar10 -d residual -f 256 --dropout 0.5 -a --lr 0.1 --wd 1e-4 \
-        --lrschedule cosine --lrcycle 250 -e 250 --run-dir runs_cifar10/odenet
+        --lrschedule cosine --lrcycle 250 -e 250 --augmentation crop+jitter+flip+norm --run-dir runs_cifar10/odenet
 """
 from __future__ import annotations
 
@@ -25,14 +31,19 @@ from torch.optim.lr_scheduler import CosineAnnealingLR, LambdaLR, ReduceLROnPlat
 
 from .head import cross_entropy      # F.cross_entropy (train.py:43,93) on the library's kernels; PyTorch's for CPU tensors
 
+AUGMENTATIONS = ('none', 'crop', 'crop+flip+norm', 'crop+jitter+flip+norm')
 SHAPES = {'mnist': (1, 28, 10), 'cifar10': (3, 32, 10), 'cifar100': (3, 32, 100), 'tiny-imagenet-200': (3, 64, 200)}
 
 
 def load_data(args):
     """`utils.load_dataset` stand-in: (x_train, y_train, x_test, y_test, in_ch, out)."""
     in_ch, side, out = SHAPES[args.dataset]
+    as_uint8 = getattr(args, 'augmentation', 'none') != 'none'      # (a run of before the flag has no such key: 'none')
     if args.data:
         blob = torch.load(args.data, map_location='cpu')
+        if as_uint8 and (blob['x_train'].dtype != torch.uint8 or blob['x_test'].dtype != torch.uint8):
+            raise SystemExit('--augmentation %s starts from the 8-bit pixels: x_train / x_test of %s must be uint8 (they are %s / %s)'
+                             % (args.augmentation, args.data, blob['x_train'].dtype, blob['x_test'].dtype))
         return blob['x_train'], blob['y_train'], blob['x_test'], blob['y_test'], blob['x_train'].shape[1], int(blob['y_train'].max()) + 1
     gen = torch.Generator().manual_seed(args.seed)
     n_tr, n_te = args.synthetic_size, max(args.batch_size, args.synthetic_size // 4)
@@ -41,6 +52,8 @@ def load_data(args):
     ytr, yte = torch.randint(0, out, (n_tr,), generator=gen), torch.randint(0, out, (n_te,), generator=gen)
     xtr = torch.randn(n_tr, in_ch, side, side, generator=gen) + means[ytr]
     xte = torch.randn(n_te, in_ch, side, side, generator=gen) + means[yte]
+    if as_uint8:      # the same set as 8-bit images: class-dependent means around mid-grey, clipped
+        xtr, xte = ((0.5 + 0.2 * x).clamp(0, 1).mul(255).round().to(torch.uint8) for x in (xtr, xte))
     return xtr, ytr, xte, yte, in_ch, out
 
 
@@ -49,6 +62,21 @@ def batches(x, y, bs, shuffle, gen):
     for i in range(0, x.shape[0], bs):
         j = idx[i:i + bs]
         yield x[j], y[j]
+
+
+def feed(data, args, shuffle, gen, epoch=0):
+    """Device batches of one pass.  `data` = (x, y) host tensors: the host loop (`batches`, one copy per batch); `data` =
+    (augment.DeviceSplit, augment.Augmenter): the split is on the device, the pass's order is uploaded ONCE (the same
+    `torch.randperm` of the same generator), and every batch is one launch of Augmenter.batch -- no copy inside a step."""
+    if isinstance(data[1], torch.Tensor):
+        for images, target in batches(data[0], data[1], args.batch_size, shuffle, gen):
+            yield images.to(args.device), target.to(args.device)
+        return
+    split, aug = data
+    n = len(split)
+    idx = torch.randperm(n, generator=gen).to(split.device) if shuffle else torch.arange(n, device=split.device)
+    for i in range(0, n, args.batch_size):
+        yield aug.batch(split, idx[i:i + args.batch_size], epoch, train=shuffle)
 
 
 class Tally:
@@ -78,7 +106,7 @@ class Tally:
         self.seen += n
 
 
-def train(data, model, optimizer, args, gen, loop=None):
+def train(data, model, optimizer, args, gen, loop=None, epoch=0):
     """One epoch; semantics of train.py:26-72 (loss read per batch, NFE counter read and reset after the forward and
     after the backward, optimizer stepped every `batch_accumulation` batches).  With `loop` (--deferred:
     integrate.DeferredLoop) the solves run with deferred completion: nothing is read back per batch, a solve that
@@ -95,13 +123,12 @@ def train(data, model, optimizer, args, gen, loop=None):
                 tally.nfe[0] += nf
                 tally.nfe[1] += nb
                 tally.batches += 1
-        for images, target in batches(data[0], data[1], args.batch_size, True, gen):
-            tally_done(loop.step(images.to(args.device), target.to(args.device)))
+        for images, target in feed(data, args, True, gen, epoch):
+            tally_done(loop.step(images, target))
         tally_done(loop.flush())
         nb = tally.batches
         return {'loss': tally.loss_sum / nb, 'acc': tally.hits / tally.seen, 'nfe-f': tally.nfe[0] / nb, 'nfe-b': tally.nfe[1] / nb}
-    for images, target in batches(data[0], data[1], args.batch_size, True, gen):
-        images, target = images.to(args.device), target.to(args.device)
+    for images, target in feed(data, args, True, gen, epoch):
         logits = model(images)
         loss = cross_entropy(logits, target)
         tally.count(logits, target, loss)
@@ -151,8 +178,7 @@ def evaluate(data, model, args):
     model.eval()
     tally = Tally()
     with torch.no_grad():
-        for images, target in batches(data[0], data[1], args.batch_size, False, None):
-            images, target = images.to(args.device), target.to(args.device)
+        for images, target in feed(data, args, False, None):
             logits = model(images)
             tally.nfe[0] += model.nfe(reset=True)
             tally.count(logits, target, cross_entropy(logits, target, reduction='sum'))
@@ -208,6 +234,8 @@ def main(argv=None):
         (('--data',), dict(type=str, default=None, help='.pt file with x_train, y_train, x_test, y_test')),
         (('--synthetic-size',), dict(type=int, default=512)),
         (('--run-dir',), dict(type=str, default=None)),
+        # utils.py:81-196 (reproduce.sh trains with crop+jitter+flip+norm), on the device: augment.py
+        (('--augmentation',), dict(type=str, choices=AUGMENTATIONS, default='none')),
         # not in the reference: solves without a read-back per batch; missed step counts are repeated, never skipped
         (('--deferred',), dict(action='store_true', default=False)),
     ]
@@ -230,6 +258,14 @@ def main(argv=None):
 
     import neural_ode_features_amd as nof
     xtr, ytr, xte, yte, in_ch, out = load_data(args)
+    if args.augmentation == 'none':
+        train_data, test_data = (xtr, ytr), (xte, yte)
+    else:
+        if in_ch != 3 and args.augmentation != 'crop':
+            raise SystemExit('--augmentation %s needs colour images: %d-channel data takes none or crop (utils.py:82-89)'
+                             % (args.augmentation, in_ch))
+        aug = nof.Augmenter(args.augmentation, dataset=args.dataset, seed=args.seed)
+        train_data, test_data = (nof.DeviceSplit(xtr, ytr, args.device), aug), (nof.DeviceSplit(xte, yte, args.device), aug)
     model = nof.ODENet(in_ch, out=out, n_filters=args.filters, downsample=args.downsample, method=args.method, tol=args.tol,
                        adjoint=args.adjoint, dropout=args.dropout, norm=args.norm).to(args.device)
     if args.optim == 'sgd':
@@ -245,7 +281,7 @@ def main(argv=None):
         best_accuracy = max(float(r['test_acc']) for r in read_log(log_path))
         print('Resuming from epoch {}: {}'.format(start_epoch, run_dir))
     else:
-        best_accuracy = evaluate((xte, yte), model, args)['test_acc']
+        best_accuracy = evaluate(test_data, model, args)['test_acc']
         start_epoch = 1
 
     if args.lrschedule == 'fixed':
@@ -259,8 +295,8 @@ def main(argv=None):
     loop = deferred_loop(model, optimizer, args) if args.deferred else None
     for epoch in range(start_epoch, args.epochs + 1):
         metrics = {'epoch': epoch}
-        metrics.update(train((xtr, ytr), model, optimizer, args, gen, loop))
-        metrics.update(evaluate((xte, yte), model, args))
+        metrics.update(train(train_data, model, optimizer, args, gen, loop, epoch))
+        metrics.update(evaluate(test_data, model, args))
         is_best = metrics['test_acc'] > best_accuracy
         best_accuracy = max(metrics['test_acc'], best_accuracy)
         params = {k: (str(v) if isinstance(v, torch.device) else v) for k, v in vars(args).items()}
