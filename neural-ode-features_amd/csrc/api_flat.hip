@@ -35,7 +35,9 @@ int flat_check(const node_flat_solve* f, FlatPlan* plan) {
     if (!sg.y || !sg.y1 || sg.n == 0) return fail(NODE_ERR_NULL, "segment %d: y / y1 is NULL or empty", i);
     for (int j = 0; j < 7; ++j)
       if (!sg.k[j]) return fail(NODE_ERR_NULL, "segment %d: stage derivative buffer %d is NULL", i, j);
-    if ((((uintptr_t)sg.y) | ((uintptr_t)sg.y1)) & 15) return fail(NODE_ERR_ARG, "segment %d: buffers must be 16-byte aligned", i);
+    uintptr_t bits = ((uintptr_t)sg.y) | ((uintptr_t)sg.y1);
+    for (int j = 0; j < 7; ++j) bits |= (uintptr_t)sg.k[j];      // (k_error_norm and k_commit read the stage derivatives as float4 too)
+    if (bits & 15) return fail(NODE_ERR_ARG, "segment %d: buffers must be 16-byte aligned", i);
   }
   *plan = flat_plan(f->ws, f->n_targets);
   if (f->ws_bytes < plan->bytes) return fail(NODE_ERR_WORKSPACE, "workspace too small: %zu < %zu", f->ws_bytes, plan->bytes);

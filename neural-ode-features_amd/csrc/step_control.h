@@ -40,7 +40,7 @@ __device__ inline void step_controller_decide(const StepCtlArgs& a, float* ratio
   for (int i = 0; i < nr; ++i) {
     const float r = ratios[i];
     if (!(r <= 1.0f)) accept = false;
-    if (r != r) nan = true;
+    if (r != r || r == INFINITY) nan = true;     // (an infinite norm -- an infinite derivative at a finite state -- is as little a ratio as a NaN)
     maxr = fmaxf(maxr, r);
     c->ratio[i] = r;
   }

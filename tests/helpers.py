@@ -182,3 +182,338 @@ def kink_free_replay(shape, envs, tol=1e-3, seed=53, t_end=1.0):
     f64 = dict(out=out_o[-1].detach().cpu(), gy=yo.grad.cpu(), gp={n: p.grad.cpu() for n, p in tw.named_parameters()})
     print('  (fp64 arbiter ran on %s)' % dev)
     return free, reps, f64
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# One dopri5 / rk4 step of the FLAT solver (csrc/api_flat.hip), restated element by element.
+#
+# What `k_lincomb`, `k_init_norms` + `k_init_controller`, `k_error_norm` + `k_step_controller`, `k_emit_flat`, `k_commit`,
+# `k_flat_scalar`, `k_flat_time` and `k_set_scalar_state` compute, as plain numpy.  Inputs are fp32 arrays; `F` is the
+# precision the arithmetic runs in: np.float64 is the REFERENCE of tests/test_gpu_step_control.py, np.float32 the same
+# statement at the kernels' precision (it only serves to MEASURE how far correct fp32 arithmetic lies from fp64, see
+# SC_DEV_* below).  The coefficients are the kernels': every tableau entry rounded to fp32 FIRST (step_control.h c_CSOL /
+# c_CERR, node_internal.h DP_CMID_F, butcher.h make_comb `(float)coef`, api_flat.hip `(float)DP_ALPHA`), then widened.
+# tests/test_step_control_host.py pins this restatement to oracle/torchdiffeq_restated.py in fp64.
+# ----------------------------------------------------------------------------------------------------------------------
+import numpy as np
+
+from oracle import torchdiffeq_restated as _tdq
+
+
+def _r32(seq):
+    return np.array(seq, dtype=np.float64).astype(np.float32)
+
+
+SC_ALPHA = _r32(_tdq.DP_ALPHA)
+SC_BETA = [_r32(row) for row in _tdq.DP_BETA]
+SC_CSOL = _r32(_tdq.DP_C_SOL)
+SC_CERR = _r32(_tdq.DP_C_ERROR)
+SC_CMID = _r32(_tdq.DP_C_MID)
+SC_RK4_ROWS = [_r32([1 / 3]), _r32([-1 / 3, 1.0]), _r32([1.0, -1.0, 1.0])]
+SC_RK4_ALPHA = _r32([1 / 3, 2 / 3, 1.0])
+SC_RK4_B = _r32([1 / 8, 3 / 8, 3 / 8, 1 / 8])
+SC_TINY_H = float(np.float32(1e-6))      # upstream's `torch.tensor(1e-6)` is an fp32 number; the kernels' 1e-6f
+SC_F0, SC_PROBE = -1, -2                 # _lib.FLAT_F0 / FLAT_PROBE
+SC_NONFINITE = -6                        # NODE_ERR_NONFINITE
+
+
+def sc_lincomb(y, ks, coef, scale, F=np.float64):
+    """y + scale * sum_j coef_j k_j as k_lincomb forms it: cf_j = scale * coef_j, s = sum cf_j k_j, y + s."""
+    y = np.asarray(y).astype(F)
+    s = np.zeros_like(y)
+    for c, k in zip(coef, ks):
+        if c != 0:
+            s = s + (F(scale) * F(c)) * np.asarray(k).astype(F)
+    return y + s
+
+
+def sc_stage(y, ks, t, dt, tsign, stage, method='dopri5', h0=None, F=np.float64):
+    """(stage state or None, stage time) of node_flat_stage: dopri5 stages 0..5, rk4 stages 1..3, SC_F0 (time only), SC_PROBE."""
+    if stage == SC_F0:
+        return None, F(tsign) * (F(t) + F(0) * F(dt))
+    if stage == SC_PROBE:
+        return sc_lincomb(y, ks[:1], [1.0], h0, F), F(tsign) * (F(t) + F(h0))
+    if method == 'dopri5':
+        row, alpha = SC_BETA[stage], SC_ALPHA[stage]
+    else:
+        row, alpha = SC_RK4_ROWS[stage - 1], SC_RK4_ALPHA[stage - 1]
+    return sc_lincomb(y, ks, row, dt, F), F(tsign) * (F(t) + F(alpha) * F(dt))
+
+
+def sc_rk4_finish(y, ks, dt, F=np.float64):
+    return sc_lincomb(y, ks, SC_RK4_B, dt, F)
+
+
+def sc_rk4_finish_scalar(v, sk, dt, F=np.float64):
+    """k_set_scalar_state(which = 1): ts_cur + (k0 + 3 k1 + 3 k2 + k3) * (dt / 8)."""
+    sk = [F(np.float32(x)) for x in sk]
+    return F(np.float32(v)) + (sk[0] + F(3) * sk[1] + F(3) * sk[2] + sk[3]) * (F(dt) * F(0.125))
+
+
+def _sc_mean(sq, F):
+    return F(np.sum(sq, dtype=F)) / F(sq.size)
+
+
+def sc_initial_step(ys, f0s, f1_of, rtol, atol, scalar=None, F=np.float64):
+    """Hairer's initial step over 1..3 segments (+ the scalar segment: scalar = (value, f0), f1_of's second result its f1).
+    `f1_of(h0)` -> (list of f1 per segment, scalar f1 or None): what the caller's dynamics return at the probe.
+    Returns dict(h0, dt, d0, d1, d2) with d* the per-segment lists (scalar last)."""
+    rtol, atol = F(np.float32(rtol)), F(np.float32(atol))
+    ys = [np.asarray(y).astype(F) for y in ys]
+    f0s = [np.asarray(f).astype(F) for f in f0s]
+    scs = [atol + np.abs(y) * rtol for y in ys]
+    d0 = [np.sqrt(_sc_mean((y / sc) ** 2, F)) for y, sc in zip(ys, scs)]
+    d1 = [np.sqrt(_sc_mean((f / sc) ** 2, F)) for f, sc in zip(f0s, scs)]
+    if scalar is not None:
+        sv, sf0 = F(np.float32(scalar[0])), F(np.float32(scalar[1]))
+        ssc = atol + abs(sv) * rtol
+        d0.append(abs(sv / ssc))
+        d1.append(abs(sf0 / ssc))
+    with np.errstate(divide='ignore', invalid='ignore'):
+        q = [a / b for a, b in zip(d0, d1)]
+    d0m, d1m = max(d0), max(d1)
+    if d0m < 1e-5 or d1m < 1e-5:
+        h0 = F(SC_TINY_H)
+    else:
+        h0 = F(0.01) * F(np.fmax.reduce(np.array(q, dtype=F)))
+    f1s, sf1 = f1_of(float(h0))
+    d2 = [np.sqrt(_sc_mean(((np.asarray(f1).astype(F) - f0) / sc) ** 2, F)) / h0 for f1, f0, sc in zip(f1s, f0s, scs)]
+    if scalar is not None:
+        d2.append(abs((F(np.float32(sf1)) - sf0) / ssc) / h0)
+    d2m = max(d2)
+    if d1m <= 1e-15 and d2m <= 1e-15:
+        h1 = max(F(SC_TINY_H), h0 * F(1e-3))
+    else:
+        h1 = (F(0.01) / max(d1m, d2m)) ** F(0.2)
+    return dict(h0=float(h0), dt=float(min(F(100) * h0, h1)), d0=d0, d1=d1, d2=d2)
+
+
+def sc_error_ratios(ys, y1s, ks, dt, rtol, atol, scalar=None, F=np.float64, cerr=None):
+    """Mean squared error ratio of every segment (the scalar segment's last; scalar = (value, [k0..k6])).
+    Returns (ratios, per-element squared ratios of the tensor segments, the scalar segment's end-of-step value or None)."""
+    cerr = SC_CERR if cerr is None else cerr
+    rtol, atol = F(np.float32(rtol)), F(np.float32(atol))
+    ratios, elems = [], []
+    for y, y1, k in zip(ys, y1s, ks):
+        y, y1 = np.asarray(y).astype(F), np.asarray(y1).astype(F)
+        e = np.zeros_like(y)
+        for j in (0, 2, 3, 4, 5, 6):
+            e = e + (F(dt) * F(cerr[j])) * np.asarray(k[j]).astype(F)
+        r = e / (atol + rtol * np.maximum(np.abs(y), np.abs(y1)))
+        elems.append(r * r)
+        ratios.append(_sc_mean(r * r, F))
+    s_new = None
+    if scalar is not None:
+        sv, sk = F(np.float32(scalar[0])), [F(np.float32(x)) for x in scalar[1]]
+        e = s = F(0)
+        for j in (0, 2, 3, 4, 5, 6):
+            e = e + (F(dt) * F(cerr[j])) * sk[j]
+            if j < 6:
+                s = s + (F(dt) * F(SC_CSOL[j])) * sk[j]
+        s_new = sv + s
+        r = e / (atol + rtol * max(abs(sv), abs(s_new)))
+        ratios.append(r * r)
+    return ratios, elems, s_new
+
+
+def sc_dt_next(dt, maxr):
+    """`_optimal_step_size` on the largest ratio: (dt_next, regime) with regime 'x10' (ratio 0), 'clamp' ([0.1, 1 / dfactor]
+    reached) or 'free'."""
+    maxr = float(maxr)
+    if maxr == 0.0:
+        return dt * 10.0, 'x10'
+    dfactor = 1.0 if maxr < 1.0 else 0.2
+    # (upstream's exponent and lower clamp are fp32 numbers, `torch.tensor(1.0 / order)`; the kernel's pow(er, 0.2) differs from that by
+    # |ln er| * 3e-9 relative, far inside the fp32 tolerance of the GPU tests)
+    factor = (maxr ** 0.5) ** float(np.float32(0.2)) / 0.9
+    clamped = min(max(factor, float(np.float32(0.1))), 1.0 / dfactor)
+    return dt / clamped, ('free' if clamped == factor else 'clamp')
+
+
+def sc_decide(ratios, t, dt, targets, j=0):
+    """The step controller's decision from the segments' ratios: accept iff every ratio <= 1; t advances when accepted; the
+    targets [j0, j1) passed (target <= t_new); done once every target is passed; a NaN or infinite ratio stops the solve."""
+    rs = [float(r) for r in ratios]
+    if any(not np.isfinite(r) for r in rs):
+        return dict(accept=False, status=SC_NONFINITE, dt_next=dt, t=t, j0=j, j1=j, done=True, regime='nonfinite', maxr=float('nan'))
+    accept = all(r <= 1.0 for r in rs)
+    maxr = max(rs)
+    dt_next, regime = sc_dt_next(dt, maxr)
+    t_new, j1 = t, j
+    if accept:
+        t_new = t + dt
+        while j1 < len(targets) and not (targets[j1] > t_new):
+            j1 += 1
+    return dict(accept=accept, status=0, dt_next=dt_next, t=t_new, j0=j, j1=j1, done=accept and j1 == len(targets),
+                regime=regime, maxr=maxr)
+
+
+def sc_dense(y0, y1, k, dt, t0, t1, target, F=np.float64, cmid=None):
+    """The quartic of `_interp_fit_dopri5` + `_interp_evaluate` at `target` in [t0, t1], in interp_one's order of operations
+    (arrays or scalars; k = the seven stage derivatives, k[1] has weight zero)."""
+    cmid = SC_CMID if cmid is None else cmid
+    conv = (lambda a: np.asarray(a).astype(F))
+    y0, y1, k, dt = conv(y0), conv(y1), [conv(a) for a in k], F(dt)
+    s = np.zeros_like(y0)
+    for j in (0, 2, 3, 4, 5, 6):
+        s = s + (dt * F(cmid[j])) * k[j]
+    ymid, f0, f1 = y0 + s, k[0], k[6]
+    x = (F(target) - F(t0)) / (F(t1) - F(t0))
+    ca = (F(-2) * dt) * f0 + (F(2) * dt) * f1 + F(-8) * y0 + F(-8) * y1 + F(16) * ymid
+    cb = (F(5) * dt) * f0 + (F(-3) * dt) * f1 + F(18) * y0 + F(14) * y1 + F(-32) * ymid
+    cc = (F(-4) * dt) * f0 + dt * f1 + F(-11) * y0 + F(-5) * y1 + F(16) * ymid
+    cd = dt * f0
+    x2 = x * x
+    x3 = x2 * x
+    x4 = x3 * x
+    return ca * x4 + cb * x3 + cc * x2 + cd * x + y0
+
+
+def sc_finish_step(st, targets, j=0, F=np.float64):
+    """One node_flat_finish_step(dopri5) on the state `st` (sc_case): the decision (sc_decide) plus 'ratios', 'rows' (dense
+    output of segment 0 for every target passed, by row), 's_new' (the scalar segment at the end of the step) and, when the step
+    ends an augmented solve, 'final' (every segment and the scalar at the last target)."""
+    ratios, _, s_new = sc_error_ratios(st['y'], st['y1'], st['k'], st['dt'], st['rtol'], st['atol'], st['scalar'], F)
+    d = sc_decide(ratios, st['t'], st['dt'], targets, j)
+    d.update(ratios=ratios, s_new=s_new, rows={}, final=None)
+    for jj in range(d['j0'], d['j1']):
+        d['rows'][jj] = sc_dense(st['y'][0], st['y1'][0], st['k'][0], st['dt'], st['t'], d['t'], targets[jj], F)
+    if d['done'] and d['status'] == 0 and st['scalar'] is not None and d['j1'] > d['j0']:
+        segs = [sc_dense(y, y1, k, st['dt'], st['t'], d['t'], targets[-1], F) for y, y1, k in zip(st['y'], st['y1'], st['k'])]
+        sk = [np.float32(x) for x in st['scalar'][1]]
+        d['final'] = (segs, sc_dense(np.float32(st['scalar'][0]), s_new, sk, st['dt'], st['t'], d['t'], targets[-1], F))
+    return d
+
+
+def sc_case(numels, ratios, seed=0, has_scalar=False, spike=None, t=0.25, dt=0.0625, rtol=1e-3, atol=1e-4):
+    """Seeded Gaussian buffers of a flat state whose segments have the mean squared error ratios `ratios` (one per tensor segment,
+    then the scalar segment's): y, y1 = y + 0.1 N(0, 1), k[0..6] ~ N(0, 1) scaled per segment -- y1 is a buffer of its own to the
+    kernels, so a segment's ratio is exactly quadratic in the scale of its k.  spike = (segment, index): that element carries
+    three quarters of its segment's sum.  ratio 0: all-zero derivatives."""
+    rng = np.random.default_rng(1000 + seed)
+    f32 = np.float32
+    ys = [rng.standard_normal(n).astype(f32) for n in numels]
+    for y in ys:
+        y[0] = 2.0        # (per-element tolerances are relative to max|y|: a segment of one or three elements must not make that tiny)
+    y1s = [(y + 0.1 * rng.standard_normal(y.size)).astype(f32) for y in ys]
+    ks = [[rng.standard_normal(n).astype(f32) for _ in range(7)] for n in numels]
+    scalar = None
+    if has_scalar:
+        scalar = (f32(rng.standard_normal()), [f32(v) for v in rng.standard_normal(7)])
+    if spike is not None:
+        sg, idx = spike
+        _, elems, _ = sc_error_ratios(ys, y1s, ks, dt, rtol, atol)
+        rr = elems[sg]
+        want = 3.0 * (rr.sum() - rr[idx])
+        tol_i = atol + rtol * max(abs(float(ys[sg][idx])), abs(float(y1s[sg][idx])))
+        e_i = np.sqrt(rr[idx]) * tol_i
+        ks[sg][6][idx] = f32(ks[sg][6][idx] + (np.sqrt(want) * tol_i + e_i) / (dt * abs(float(SC_CERR[6]))))
+    for _ in range(30):
+        got, _, _ = sc_error_ratios(ys, y1s, ks, dt, rtol, atol, scalar)
+        for i, (g, w) in enumerate(zip(got, ratios)):
+            sc = 0.0 if w == 0 else float(np.sqrt(w / g))
+            if i < len(numels):
+                ks[i] = [(k.astype(np.float64) * sc).astype(f32) for k in ks[i]]
+            else:
+                scalar = (scalar[0], [f32(float(v) * sc) for v in scalar[1]])
+        if all(w == 0 or abs(g / w - 1) < 1e-3 for g, w in zip(got, ratios)):
+            break
+    return dict(y=ys, y1=y1s, k=ks, scalar=scalar, t=t, dt=dt, rtol=rtol, atol=atol, numels=list(numels))
+
+
+# The sizes at which the kernels' indexing changes (derivation: tests/test_gpu_step_control.py)
+SC_SMALL = [1, 3, 4, 5, 255, 1027]
+SC_N_INIT = 131072 + 1
+SC_N_ERR = 524288 + 5
+SC_N_COMMIT = 2097152 + 5
+
+# (name, sc_case arguments, band): band 'free' = accepted, dt_next unclamped (largest ratio in [0.01, 0.3]); 'clamp' = accepted,
+# dt_next == dt (ratio in [0.45, 0.85]); 'reject' = rejected, unclamped ([2, 1e4]); 'huge' = rejected, dt / 5; 'zero' = dt x 10
+SC_STEP_CASES = (
+    [('n%d' % n, dict(numels=[n], ratios=[0.1], seed=n), 'free') for n in SC_SMALL] +
+    [('sweep2', dict(numels=[SC_N_ERR], ratios=[0.2], seed=7), 'free'),
+     ('commit2', dict(numels=[SC_N_COMMIT], ratios=[0.15], seed=8), 'free')] +
+    [('spike1027_%d' % i, dict(numels=[1027], ratios=[0.1 if i % 2 == 0 else 50.0], seed=20 + i, spike=(0, i)),
+      'free' if i % 2 == 0 else 'reject') for i in (0, 1020, 1023, 1024, 1025, 1026)] +
+    [('spikebig_%d' % i, dict(numels=[SC_N_ERR], ratios=[0.1], seed=30, spike=(0, i)), 'free')
+     for i in (0, SC_N_ERR - 5, SC_N_ERR - 2, SC_N_ERR - 1)] +
+    [('seg3_last_rejects', dict(numels=[SC_N_ERR, 7, 1], ratios=[0.2, 0.2, 50.0], seed=40), 'reject'),
+     ('seg3_middle_max', dict(numels=[SC_N_ERR, 7, 1], ratios=[0.05, 0.2, 0.1], seed=41), 'free'),
+     ('seg2', dict(numels=[5, 1027], ratios=[0.05, 0.2], seed=42), 'free'),
+     ('seg2_scalar_rejects', dict(numels=[5, 1027], ratios=[0.2, 0.2, 5.0], seed=43, has_scalar=True), 'reject'),
+     ('seg2_scalar', dict(numels=[5, 1027], ratios=[0.1, 0.05, 0.2], seed=44, has_scalar=True), 'free'),
+     ('seg3_scalar', dict(numels=[SC_N_ERR, 7, 1], ratios=[0.1, 0.05, 0.2, 0.1], seed=46, has_scalar=True), 'free'),
+     ('seg2_scalar_small', dict(numels=[5, 1027], ratios=[0.2, 0.1, 0.05], seed=45, has_scalar=True), 'free'),
+     ('clamp', dict(numels=[1027], ratios=[0.65], seed=50), 'clamp'),
+     ('huge', dict(numels=[255], ratios=[1e9], seed=51), 'huge'),
+     ('zero', dict(numels=[1027], ratios=[0.0], seed=52), 'zero')])
+SC_BANDS = {'free': (0.01, 0.3), 'clamp': (0.45, 0.85), 'reject': (2.0, 1e4), 'huge': (4.5 ** 10 * 1.1, float('inf')), 'zero': (0.0, 0.0)}
+
+
+def sc_init_case(name):
+    """Inputs of the initial-step cases: dict(y, f0, f1 (lists per segment), scalar = (value, f0, f1) or None)."""
+    rng = np.random.default_rng(sum(map(ord, name)))
+    f32 = np.float32
+    g = (lambda n, s=1.0: (s * rng.standard_normal(n)).astype(f32))
+    scalar = None
+    if name.startswith('n'):                       # ordinary, one segment of the given size
+        n = int(name[1:])
+        y, f0 = [g(n)], [g(n)]
+        f1 = [(f0[0] + g(n, 0.01)).astype(f32)]
+    elif name == 'y_zero':                         # d0 < 1e-5: h0 = 1e-6
+        y, f0 = [np.zeros(1027, f32)], [g(1027)]
+        f1 = [(f0[0] + g(1027, 1e-4)).astype(f32)]
+    elif name == 'f_zero':                         # d1, d2 <= 1e-15
+        y, f0, f1 = [g(1027)], [np.zeros(1027, f32)], [np.zeros(1027, f32)]
+    elif name == 'seg3':                           # segment 0: max d0 / d1; segment 1: max d1; segment 2: max d2
+        y = [g(SC_N_INIT, 4.0), g(7), g(1)]
+        f0 = [g(SC_N_INIT, 0.5), g(7, 8.0), g(1)]
+        f1 = [(f0[0] + g(SC_N_INIT, 1e-3)).astype(f32), (f0[1] + g(7, 1e-3)).astype(f32), (f0[2] + f32(0.5)).astype(f32)]
+    elif name == 'scalar_max':                     # the scalar segment supplies every maximum
+        y, f0 = [g(5, 1e-3), g(1027, 1e-3)], [g(5, 1e-3), g(1027, 1e-3)]
+        f1 = [(a + g(a.size, 1e-6)).astype(f32) for a in f0]
+        scalar = (f32(40.0), f32(20.0), f32(29.0))
+    elif name == 'seg2_scalar':                    # scalar present, maxima from the tensors
+        y, f0 = [g(5), g(1027)], [g(5), g(1027)]
+        f1 = [(a + g(a.size, 1e-2)).astype(f32) for a in f0]
+        scalar = (f32(0.005), f32(0.02), f32(0.02 + 1e-6))
+    else:
+        raise KeyError(name)
+    return dict(y=y, f0=f0, f1=f1, scalar=scalar)
+
+
+SC_INIT_CASES = ['n%d' % n for n in SC_SMALL + [SC_N_INIT]] + ['y_zero', 'f_zero', 'seg3', 'scalar_max', 'seg2_scalar']
+SC_INIT_TOL = (1e-3, 1e-4)                        # rtol, atol of the initial-step cases
+
+# Largest relative deviation of the SAME restatement run in fp32 on the CPU from its fp64 run, over the cases above (measured by
+# tests/test_step_control_host.py, which asserts that they still hold): what correct fp32 arithmetic costs.  The kernels sum in
+# another order, so they get 8 x these (tests/test_gpu_step_control.py); nothing here comes from a kernel's output.
+SC_DEV_RATIO = 5e-7  # measured 4.6e-7:   # mean squared error ratio of a segment
+SC_DEV_INIT = 1.6e-7  # measured 1.53e-7:    # h0 and the initial dt
+SC_DEV_STAGE = 6e-8  # measured 5.9e-8:   # a stage state / RK4 update per element, relative to max|y|; a stage time, relative
+SC_DEV_DENSE = 4.2e-6  # measured 4.13e-6:   # dense output per element, relative to max|y|
+
+
+def sc_advance(st, d, dt_next):
+    """The state after an accepted step that did not end the solve (k_commit + the controller's scalar bookkeeping): y <- y1,
+    k0 <- k6 (FSAL), the scalar segment likewise; t and dt move on.  Every other buffer is the caller's and stays."""
+    new = dict(st)
+    new['y'] = [a.copy() for a in st['y1']]
+    new['k'] = [[k[6].copy()] + [a.copy() for a in k[1:]] for k in st['k']]
+    if st['scalar'] is not None:
+        sk = list(st['scalar'][1])
+        new['scalar'] = (np.float32(d['s_new']), [sk[6]] + sk[1:])
+    new['t'], new['dt'] = d['t'], dt_next
+    return new
+
+
+SC_DENSE_SIZES = [5, 1027, SC_N_ERR]
+
+
+def sc_dense_scenario(n):
+    """Three consecutive steps on one state: the first passes THREE targets (the last one exactly t + dt), the second ONE, the
+    third NONE.  Returns (state, targets)."""
+    st = sc_case([n], [0.05], seed=60 + n % 97)
+    dt2, _ = sc_dt_next(st['dt'], 0.05)
+    t, dt = st['t'], st['dt']
+    return st, [t + 0.3 * dt, t + 0.5 * dt, t + dt, t + dt + 0.5 * dt2, t + 10.0]

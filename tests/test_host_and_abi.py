@@ -82,6 +82,24 @@ def test_new_entry_points_check_their_arguments_without_a_gpu():
     assert lib.node_flat_finish_step(C.byref(f), 0, None, None) == -9 and b'nseg' in lib.node_last_error()
     f.nseg = 1
     assert lib.node_flat_finish_step(C.byref(f), 0, None, None) == -9 and b'workspace' in lib.node_last_error()
+    # every buffer a kernel reads as float4 must be 16-byte aligned: y, y1 and each of the seven stage derivatives (addresses only,
+    # the checks come before any HIP call)
+    f.ws, f.ws_bytes = 0x10000, 0
+    sg = f.seg[0]
+    sg.y, sg.y1, sg.n = 0x20000, 0x30000, 8
+    for j in range(7):
+        sg.k[j] = 0x40000 + 0x1000 * j
+    assert lib.node_flat_finish_step(C.byref(f), 0, None, None) == -4            # aligned everywhere: only the workspace is too small
+    for field in ('y', 'y1'):
+        setattr(sg, field, getattr(sg, field) + 4)
+        assert lib.node_flat_finish_step(C.byref(f), 0, None, None) == -9 and b'16-byte' in lib.node_last_error()
+        setattr(sg, field, getattr(sg, field) - 4)
+    for j in range(7):
+        sg.k[j] += 4
+        assert lib.node_flat_initial_step(C.byref(f), 0, None) == -9 and b'16-byte' in lib.node_last_error()
+        assert lib.node_flat_finish_step(C.byref(f), 0, None, None) == -9 and b'16-byte' in lib.node_last_error()
+        sg.k[j] -= 4
+    assert lib.node_flat_finish_step(C.byref(f), 0, None, None) == -4
     assert os.path.basename(_lib.LIB_PATH) == 'libnode_hip.so' and os.path.basename(_lib.LIB_DIAG_PATH) == 'libnode_hip_diag.so'
 
 
