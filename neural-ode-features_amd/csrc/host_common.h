@@ -27,12 +27,7 @@ int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
     if (_rc != NODE_OK) return _rc; \
   } while (0)
 
-// an integer switch of the environment (NODE_TUNE_*).  `static const int x = env_int(...)` reads it once per process;
-// a plain call reads it again every time.
-inline int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
+// (the environment switches' one reader, env_int: node_internal.h -- the kernel units' launchers read switches too)
 
 // the tiling geometry of a shape (dims.hip); refuses what no kernel is instantiated for
 int dims_for(const node_shape* sh, Dims* out);

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) {
   if (lane == 0) { red[wave * 2] = loss_n; red[wave * 2 + 1] = hit; }
   __syncthreads();
   // workgroup partial -> scratch; the last workgroup to arrive sums the partials in index order.  Fence-free hand-off
-  // as in k_theta_finalize (kernels_pointwise.hip): agent-scope store, acknowledged, then the agent-scope count; the
+  // as in k_theta_finalize (kernels_theta_finalize.hip): agent-scope store, acknowledged, then the agent-scope count; the
   // reader uses agent-scope loads.  Tied to gfx950 (agent-scope stores write through the XCD's L2).
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(__gfx950__)
 #error "k_head_loss_fwd's fence-free hand-off is only valid on gfx950"

@@ -871,8 +871,7 @@ int stem_gn_cb(int HW, int C, int cpg) {
   while (cb < cpg) cb *= 2;
   if (cb > C || cb > 128 || (size_t)HW * cb * 2 * sizeof(float) > budget) return 0;
   while (cb * 2 <= C && cb * 2 <= 128 && (size_t)HW * cb * 4 * sizeof(float) <= budget) cb *= 2;
-  static int cap = -2;      // NODE_TUNE_STEM_GNCB: upper limit of the channel block (A/B measurements)
-  if (cap == -2) { const char* e = getenv("NODE_TUNE_STEM_GNCB"); cap = e ? atoi(e) : -1; }
+  static const int cap = env_int("NODE_TUNE_STEM_GNCB", -1);      // upper limit of the channel block (A/B measurements)
   while (cap > 0 && cb > cap && cb / 2 >= cpg && cb / 2 >= 8) cb /= 2;
   // the kernels index channels with `t & (CB - 1)`, run C / CB blocks per sample and CB / cpg whole groups per block:
   // a block that does not divide C leaves channels unwritten, a group that straddles blocks gets wrong statistics

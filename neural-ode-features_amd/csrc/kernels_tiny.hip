@@ -404,8 +404,7 @@ int tiny_slice_channels(const Dims& d) {
   // measured (profiles/r05_latency_bs1.txt): images of up to 64 pixels win a little (36.7 -> 33.8 us per evaluation at [1,256,8,8]);
   // at 16x16 the eight-slice hand-off and four tiles per wave lose to the F(4x4,3x3) path (72 vs 39 us), so those keep it
   // unless NODE_TUNE_TINY=1 forces the latency kernels (tests)
-  static int force = -2;
-  if (force == -2) { const char* e = getenv("NODE_TUNE_TINY"); force = e ? atoi(e) : -1; }
+  static const int force = env_int("NODE_TUNE_TINY", -1);
   if (force != 1 && d.HW > 64) return 0;
   int CS = (d.HW <= 100 && d.C % 64 == 0) ? 64 : 32;
   if (d.C / CS > TINY_MAXKS) CS = 64;

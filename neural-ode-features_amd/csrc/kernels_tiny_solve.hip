@@ -824,8 +824,7 @@ finished:
 // (a power of two <= 16 channels per group), an image of <= 64 pixels (one pixel tile per wave), a grid that fits the chip
 // one workgroup per CU.  NODE_TUNE_TINY_RESIDENT=0 keeps the two-launches-per-evaluation path.
 bool tiny_resident_ok(const Dims& d) {
-  const char* e = getenv("NODE_TUNE_TINY_RESIDENT");      // (read per solve, not per launch: tests switch it inside one process)
-  if (e != nullptr && atoi(e) == 0) return false;
+  if (env_int("NODE_TUNE_TINY_RESIDENT", 1) == 0) return false;      // (read per solve, not per launch: tests switch it inside one process)
   if (d.C % 32 != 0 || d.C > 256 || d.HW > 64 || d.W > 62) return false;
   if (d.cpg < 1 || d.cpg > 16 || (d.cpg & (d.cpg - 1)) != 0) return false;
   // compute units of the CURRENT device (cached per device: a process may drive several), one workgroup each -- the kernel's LDS
@@ -868,7 +867,7 @@ void launch_tiny_solve(const Dims& d, const TinyResidentArgs& b, hipStream_t s) 
   }
   a.ctrl = b.ctrl; a.ctrl_host = b.ctrl_host; a.nonce = b.nonce;
   for (int i = 0; i < 8; ++i) a.targets_inline[i] = b.targets_inline[i];
-  { const char* e = getenv("NODE_TUNE_TINY_STAMPS"); a.stamps = e ? atoi(e) : 0; }
+  a.stamps = env_int("NODE_TUNE_TINY_STAMPS", 0);
   for (int i = 0; i < 3; ++i) { a.gamma[i] = b.gamma[i]; a.beta[i] = b.beta[i]; }
   a.targets = b.targets; a.n_targets = b.n_targets; a.forced = b.forced; a.n_forced = b.n_forced;
   a.dt_log = b.dt_log; a.dt_log_cap = b.dt_log_cap; a.t0 = b.t0; a.max_steps = b.max_steps;
@@ -879,7 +878,7 @@ void launch_tiny_solve(const Dims& d, const TinyResidentArgs& b, hipStream_t s) 
   static bool attr[MAX_DEVICES] = {};
   allow_full_lds(reinterpret_cast<const void*>(k_tiny_solve), attr);
   int grid = d.N * a.GP * a.KS;
-  { const char* e = getenv("NODE_TUNE_TINY_RESIDENT"); if (e != nullptr && atoi(e) == 2 && grid > 1) --grid; }    // test hook: a grid that is NOT whole -- every wait must run into its deadline, the grid must drain
+  if (env_int("NODE_TUNE_TINY_RESIDENT", 1) == 2 && grid > 1) --grid;    // test hook: a grid that is NOT whole -- every wait must run into its deadline, the grid must drain
   hipLaunchKernelGGL(k_tiny_solve, dim3(grid), dim3(256), lds, s, a);
 }
 

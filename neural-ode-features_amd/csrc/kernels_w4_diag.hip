@@ -459,9 +459,8 @@ __global__ __launch_bounds__(256, 2) void k_w4_gemm64k(const float* __restrict__
 }
 
 // ---- the hook of w4_select.hip
-static int w4_diag_env(const char* name) { const char* e = getenv(name); return e ? atoi(e) : 0; }
 void w4_diag_switches(W4Switches& sw) {
-  sw.early = w4_diag_env("NODE_TUNE_W4_EARLY");
+  sw.early = env_int("NODE_TUNE_W4_EARLY", 0);
   const char* e = getenv("NODE_TUNE_W4_STAMPS");
   sw.stamps = e != nullptr ? reinterpret_cast<unsigned long long*>(strtoull(e, nullptr, 0)) : nullptr;
 }
@@ -469,17 +468,17 @@ void w4_diag_switches(W4Switches& sw) {
 bool launch_w4_gemm_variant(const W4Switches& sw, const float* V, const unsigned short* Ub, float* M, const Ctrl* ctrl, const W4Geom& gm,
                             hipStream_t s) {
   const int N = gm.N, C = gm.C;
-  if (w4_diag_env("NODE_TUNE_W4_KSPLIT") != 0 && C == 256) {   // two waves per SIMD, a tile's K range in two halves
+  if (env_int("NODE_TUNE_W4_KSPLIT", 0) != 0 && C == 256) {   // two waves per SIMD, a tile's K range in two halves
     hipLaunchKernelGGL(k_w4_gemm64k, dim3(64 * (N / 16)), dim3(256), 8 * 1024 * sizeof(float), s, V, Ub, M, ctrl, gm, sw.stamps);
     return true;
   }
-  if (w4_diag_env("NODE_TUNE_W4_LDS") != 0 && C == 256 && N % 32 == 0) {      // the own component's operands through an LDS-DMA ring
+  if (env_int("NODE_TUNE_W4_LDS", 0) != 0 && C == 256 && N % 32 == 0) {      // the own component's operands through an LDS-DMA ring
     static bool attrl[MAX_DEVICES] = {};
     allow_full_lds(reinterpret_cast<const void*>(k_w4_gemm64l), attrl);
     hipLaunchKernelGGL(k_w4_gemm64l, dim3((N / 16) * (C >> 6) * 8), dim3(256), (size_t)W4L_NS * W4L_SLOT, s, V, Ub, M, ctrl, gm, sw.stamps);
     return true;
   }
-  if (w4_diag_env("NODE_TUNE_W4_HALF") != 0 && C == 256 && sw.sharev == 1) {    // half-height tiles, two waves per SIMD (bit-identical)
+  if (env_int("NODE_TUNE_W4_HALF", 0) != 0 && C == 256 && sw.sharev == 1) {    // half-height tiles, two waves per SIMD (bit-identical)
     hipLaunchKernelGGL(k_w4_gemm32b, dim3((N / 8) * 4 * 8), dim3(256), 4 * 1024 * sizeof(float), s, V, Ub, M, ctrl, gm);
     return true;
   }

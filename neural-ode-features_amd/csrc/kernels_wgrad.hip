@@ -859,8 +859,7 @@ size_t wgrad_lds_bytes(const Dims& d) {
 
 int wgrad_variant() {
   if (g_wgrad_variant >= 0) return g_wgrad_variant;
-  static int v = -1;
-  if (v < 0) { const char* e = getenv("NODE_TUNE_WGRAD_VARIANT"); v = e ? atoi(e) : 1; }
+  static const int v = env_int("NODE_TUNE_WGRAD_VARIANT", 1);
   return v;
 }
 

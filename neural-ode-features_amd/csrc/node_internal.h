@@ -4,8 +4,16 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <cstdlib>
 
 namespace node {
+
+// an integer switch of the environment (NODE_TUNE_*).  `static const int x = env_int(...)` reads it once per process;
+// a plain call reads it again every time.
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
 
 // ----------------------------------------------------------------------------
 // Geometry
@@ -272,10 +280,6 @@ struct ErrSeg {
 constexpr int ERR_BLOCKS = 512;
 // all segments of the state in one launch (grid.y = segment)
 void launch_error_norm(const ErrSeg* segs, float* const* partial /*[ERR_BLOCKS] each*/, int nseg, const Ctrl* ctrl, float rtol, float atol, hipStream_t s);
-// ... with the step controller as the LAST-ARRIVING workgroup of the same launch (round 6: one launch and one kernel boundary less per
-// step): `arrive` = a device word that is zero before the launch (the last workgroup zeroes it again)
-struct StepCtlArgs;
-void launch_error_norm_ctl(const ErrSeg* segs, float* const* partial, int nseg, const StepCtlArgs& ctl, unsigned* arrive, hipStream_t s);
 
 struct StepCtlArgs {
   Ctrl* ctrl;
@@ -341,8 +345,6 @@ void launch_export_record(const Ctrl* ctrl, node_step_record* rec, float* miss_f
 // initial step (Hairer)
 struct InitSeg { const float* y0; const float* f0; const float* f1; size_t n; };
 void launch_init_norms(const InitSeg* segs, float* const* partial /*[ERR_BLOCKS][2] each*/, int nseg, float rtol, float atol, int phase, hipStream_t s);
-struct InitCtlArgs;
-void launch_init_norms_ctl(const InitSeg* segs, float* const* partial, int nseg, const InitCtlArgs& ctl, unsigned* arrive, hipStream_t s);
 struct InitCtlArgs {
   Ctrl* ctrl;
   const float* partial[3];
@@ -392,7 +394,14 @@ struct ConvArgs {
   unsigned long long* stamps;  // diagnostics only (NODE_STAMPS builds); nullptr otherwise
   int ablate;                  // diagnostics only (NODE_STAMPS builds): timing-only ablation bits
 };
-void launch_conv(const Dims& d, const ConvArgs& a, hipStream_t s);
+void launch_conv(const Dims& d, const ConvArgs& a, hipStream_t s);    // conv_select.hip: the kernel family Dims::wino names
+// the families behind it (kernels_conv_{direct,wino1d,wino2d}.hip): launcher (Dims::BM picks the instantiation) and LDS bytes of a launch
+void launch_conv_direct(const Dims& d, const ConvArgs& a, hipStream_t s);
+void launch_conv_w(const Dims& d, const ConvArgs& a, hipStream_t s);
+void launch_conv_w2(const Dims& d, const ConvArgs& a, hipStream_t s);
+size_t conv_direct_lds_bytes(const Dims& d);
+size_t conv_w_lds_bytes(const Dims& d);
+size_t conv_w2_lds_bytes(const Dims& d);
 // tuning (tools/kbench.hip): kernel variant override (<0: production choice)
 extern int g_wgrad_variant;
 extern int g_conv_bm;      // force the conv M tile (64 / 128) where the geometry allows; <= 0: heuristic

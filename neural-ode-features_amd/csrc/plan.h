@@ -8,7 +8,6 @@ namespace node {
 struct Plan {
   // common
   Ctrl* ctrl;
-  unsigned* arrive;         // arrival counter of the norm kernels whose last workgroup is the controller (zero between launches)
   float* partial[3];        // [ERR_BLOCKS][2] each
   float* wf[2];             // packed forward weights
   float* wd[2];             // packed dgrad weights (adjoint)
@@ -26,8 +25,9 @@ struct Plan {
   unsigned short* w4ub[4];  // the same as exact bf16 triples (k_w4_gemm64b)
   float* tmapS[2];          // the border maps in the W4S blocking (kernels_w4s.hip)
   W4Scales* w4sc;           // power-of-two scales of the fp16-pair operands (wino4.h)
-  float* W4Va0b;            // second copy of W4Va[0]: the pass that ends an evaluation writes the NEXT one's conv-1 operand while this
-                            // evaluation's weight gradient may still read its own (side stream, Solver::wgrad_side)
+  float* W4Va0b;            // second copy of W4Va[0]: the pass that ends an evaluation writes the NEXT one's conv-1 operand into the set
+                            // this evaluation's weight gradient does not read (Solver::va0_of).  On one stream the weight gradient is
+                            // enqueued in front of that pass; whether one copy would do is open
   float *W4Va[2], *W4Z[2], *W4dU;   // F(4x4,3x3)-domain weight gradient (C % 128 == 0): the forward convs' row operands
                                     // kept until it runs, Z = A dz A^T of both conv outputs' cotangents, the gradients
   float *act1b, *xh1b, *r1b;   // second set of GroupNorm-1's saved tensors: the pass that ends evaluation s also forms

@@ -10,7 +10,6 @@ Plan make_plan(const Dims& d, int adjoint, int n_t, void* base) {
   memset(&p, 0, sizeof(p));
   Bump b(base);
   p.ctrl = b.take<Ctrl>(1);
-  p.arrive = b.take<unsigned>(4);
   p.targets = b.take<double>((size_t)(n_t > 0 ? n_t : 1));
   p.forced = b.take<double>(STEP_LIST_CAP);
   p.dtlog = b.take<double>(STEP_LIST_CAP);

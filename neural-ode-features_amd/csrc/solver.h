@@ -25,7 +25,6 @@ struct StepGuess { int N, C, H, W, aug, forced; float rtol, atol; double t0, t1;
 int guess_steps(const StepGuess& k);
 void remember_steps(const StepGuess& k);
 
-struct SideStream;                             // a second stream for the weight gradient (solver.hip, Solver::side)
 extern int g_w4_pair_stats[4];                 // node_w4_pair_stats (diagnostics; process-wide: a backward pass runs on autograd's thread)
 extern std::atomic<int> g_resident_cooldown;   // solves left before the resident latency path is tried again (Solver::choose_resident)
 
@@ -85,11 +84,6 @@ struct Solver {
   bool w4_f16 = false;     // ... both operands as fp16 pairs (k_w4_gemm64h; wino4.h), decided in prepare()
   bool w4_f16_aug = false; // set by the caller before prepare(): an augmented solve may use them (adaptive dopri5 solves: the cotangent-side
                            // scale follows the data through the step controller)
-  // The fp16-pair weight gradient (k_w4_wgrad64h: two small workgroups per CU, <= 128 registers) on a SIDE stream beside the data
-  // gradient of conv 1 and the pass behind it (k_w4_gemm64h: one 332-register wave per SIMD, which leaves it room): forked behind the
-  // pass that wrote Z1, joined in front of k_theta_finalize.  NODE_TUNE_W4_WGRAD_SIDE = 0 / 1 (read per solve in prepare()).
-  SideStream* side = nullptr;
-  bool side_pending = false;
   float* va0_of(int set) const { return (set && p.W4Va0b != nullptr) ? p.W4Va0b : p.W4Va[0]; }
   bool g_ready = false;    // the cotangent-side scale is known (behind an interval's first evaluation, launch_w4_gscale)
   // the format of the evaluation being enqueued: forward solves always pairs; augmented ones once the cotangent scale is known
@@ -121,10 +115,6 @@ struct Solver {
   void take_norm_hook(const node_solve_opts* o);
   // this rank's sums of the coming decision -> nr_buf, summed over the ranks by the hook (both enqueued on the solve's stream)
   void norm_exchange(int mode, int nseg);
-  // NODE_TUNE_FOLD_CTL = 1: the controllers as the LAST-ARRIVING workgroup of the norm kernels (k_error_norm_ctl, k_init_norms_ctl: eight
-  // launches less per training step).  Built for the round-5 review's item 5 and measured: 27 940 against 28 110 images/s at cfg 2 -- the
-  // last workgroup's coherent re-read of the partial sums behind the arrival chain costs what the launch boundary did.  Off by default.
-  static bool fold_ctl();
 
   double conv_flops() const { return 2.0 * 9.0 * d.C * d.C * (double)d.N * d.HW; }
   int check_launch(const char* what);

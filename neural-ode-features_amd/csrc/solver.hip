@@ -39,34 +39,6 @@ const double DP_BETA[6][6] = {
     {35.0 / 384, 0, 500.0 / 1113, 125.0 / 192, -2187.0 / 6784, 11.0 / 84},
 };
 
-// A second stream for the weight gradient of an augmented evaluation (Solver::wgrad_side): one per host thread and device, created at
-// first use and kept (stream creation costs milliseconds).
-struct SideStream {
-  int dev = -1;
-  hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;
-};
-static thread_local SideStream g_side;
-static bool get_side(SideStream** out) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); return false; }
-  if (g_side.s != nullptr && g_side.dev != dev) {
-    (void)hipEventDestroy(g_side.fork); (void)hipEventDestroy(g_side.join); (void)hipStreamDestroy(g_side.s);
-    g_side = SideStream();
-  }
-  if (g_side.s == nullptr) {
-    if (hipStreamCreateWithFlags(&g_side.s, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&g_side.fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&g_side.join, hipEventDisableTiming) != hipSuccess) {
-      (void)hipGetLastError();
-      g_side = SideStream();
-      return false;
-    }
-    g_side.dev = dev;
-  }
-  *out = &g_side;
-  return true;
-}
 int g_w4_pair_stats[4] = {0, -1, 0, 0};
 static thread_local Ctrl* g_blind_resident_ctrl = nullptr;   // pinned: where a DEFERRED resident solve leaves its record for this library itself --
                                                        // the caller reads the device record; a later call of this thread arms the cooldown from this one
@@ -163,10 +135,6 @@ void Solver::norm_exchange(int mode, int nseg) {
   nr_fn(nr_ctx, nr_buf, 8, (void*)st);
 }
 
-bool Solver::fold_ctl() {
-  return env_int("NODE_TUNE_FOLD_CTL", 0) != 0;
-}
-
 int Solver::check_launch(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));
@@ -182,7 +150,6 @@ int Solver::prepare() {
   float* zr[12];
   size_t zn[12];
   int nz = 0;
-  zr[nz] = reinterpret_cast<float*>(p.arrive); zn[nz++] = 4;
   if (aug) {
     zr[nz] = p.KT[1]; zn[nz++] = d.P;
     zr[nz] = p.sred + (size_t)2 * 9 * d.C + 2 * ((9 * (size_t)d.C + 63) / 64); zn[nz++] = 1;
@@ -209,10 +176,6 @@ int Solver::prepare() {
     w4_b16 = w4_uses_bf16(d.N8, d.C);
     w4_f16 = w4_b16 && w4_f16_fits(d.N8, d.C) && (!aug || (w4_f16_aug && w4_wgrad_on() && w4_wgrad_f16_fits(d.N8, d.C)));
     g_ready = false;
-    side = nullptr; side_pending = false;
-    if (w4_f16 && aug) {
-      if (env_int("NODE_TUNE_W4_WGRAD_SIDE", 0) != 0 && !get_side(&side)) side = nullptr;
-    }
     if (w4_f16) { zr[nz] = reinterpret_cast<float*>(p.w4sc); zn[nz++] = sizeof(W4Scales) / sizeof(float); }
   }
   // (first: it carries the solve's zero fills, among them the scratch words of k_w4_scales)
@@ -388,18 +351,9 @@ int Solver::eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_
     w4_pass(2, 0, a);
   }
   if (need_theta && wg4 && f16_now()) {
-    hipStream_t ws = st;
-    if (side != nullptr) {        // fork: the weight gradient runs beside the data gradient of conv 1 and its pass
-      (void)hipEventRecord(side->fork, st);
-      (void)hipStreamWaitEvent(side->s, side->fork, 0);
-      ws = side->s;
-    }
-    {
-      ProfScope ps(1, 2.0 * conv_flops(), ws);
-      launch_w4_wgrad_f16(reinterpret_cast<const unsigned*>(va0_of(cur)), reinterpret_cast<const unsigned*>(p.W4Z[0]), reinterpret_cast<const unsigned*>(p.W4Va[1]),
-                          reinterpret_cast<const unsigned*>(p.W4Z[1]), p.W4dU, p.ctrl, d.N8, d.C, &p.w4sc->e[W4_E_V1], &p.w4sc->e[W4_E_V2], &p.w4sc->e[W4_E_G], ws);
-    }
-    if (side != nullptr) { (void)hipEventRecord(side->join, side->s); side_pending = true; }
+    ProfScope ps(1, 2.0 * conv_flops(), st);
+    launch_w4_wgrad_f16(reinterpret_cast<const unsigned*>(va0_of(cur)), reinterpret_cast<const unsigned*>(p.W4Z[0]), reinterpret_cast<const unsigned*>(p.W4Va[1]),
+                        reinterpret_cast<const unsigned*>(p.W4Z[1]), p.W4dU, p.ctrl, d.N8, d.C, &p.w4sc->e[W4_E_V1], &p.w4sc->e[W4_E_V2], &p.w4sc->e[W4_E_G], st);
   } else if (need_theta && wg4) {
     W4WgradArgs wa;
     memset(&wa, 0, sizeof(wa));
@@ -433,7 +387,6 @@ int Solver::eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_
     }
   }
   if (!need_theta) return check_launch("augmented dynamics (F(4x4,3x3))");
-  if (side_pending) { (void)hipStreamWaitEvent(st, side->join, 0); side_pending = false; }      // join: dU is complete
   ThetaFinalizeArgs tf;
   memset(&tf, 0, sizeof(tf));
   tf.dU = wg4 ? p.W4dU : nullptr;
@@ -599,22 +552,15 @@ int Solver::initial_step() {
   ic.ctrl = p.ctrl;
   for (int i = 0; i < nseg; ++i) { ic.partial[i] = p.partial[i]; ic.numel[i] = (double)segs[i].n; }
   ic.nseg = nseg; ic.has_scalar = aug ? 1 : 0; ic.phase = 0; ic.rtol = rtol; ic.atol = atol;
-  const bool fold = nr_fn == nullptr && fold_ctl();     // norms + decision as one launch (the last workgroup decides)
-  if (fold) launch_init_norms_ctl(segs, p.partial, nseg, ic, p.arrive, st);
-  else {
-    launch_init_norms(segs, p.partial, nseg, rtol, atol, 0, st);
-    if (nr_fn != nullptr) { norm_exchange(1, nseg); ic.gbuf = nr_buf; ic.gworld = nr_world; }
-    launch_init_controller(ic, st);
-  }
+  launch_init_norms(segs, p.partial, nseg, rtol, atol, 0, st);
+  if (nr_fn != nullptr) { norm_exchange(1, nseg); ic.gbuf = nr_buf; ic.gworld = nr_world; }
+  launch_init_controller(ic, st);
   const double one[1] = {1.0};
   TRY(eval_sys(1, one, 1, SC_H0, et_probe(), false));
   ic.phase = 1;
-  if (fold) launch_init_norms_ctl(segs, p.partial, nseg, ic, p.arrive, st);
-  else {
-    launch_init_norms(segs, p.partial, nseg, rtol, atol, 1, st);
-    if (nr_fn != nullptr) norm_exchange(2, nseg);
-    launch_init_controller(ic, st);
-  }
+  launch_init_norms(segs, p.partial, nseg, rtol, atol, 1, st);
+  if (nr_fn != nullptr) norm_exchange(2, nseg);
+  launch_init_controller(ic, st);
   return check_launch("initial step");
 }
 
@@ -651,13 +597,9 @@ int Solver::enqueue_step(const StepIO& io) {
   sc.dt_log = io.log_cap > 0 ? p.dtlog : nullptr; sc.dt_log_cap = io.log_cap;
   sc.interp_scalar = aug ? 1 : 0;
   sc.w4sc = (aug && w4_f16) ? p.w4sc : nullptr;
-  if (nr_fn == nullptr && fold_ctl()) {
-    launch_error_norm_ctl(es, p.partial, nseg, sc, p.arrive, st);     // the last-arriving workgroup of the error norm is the controller
-  } else {
-    launch_error_norm(es, p.partial, nseg, p.ctrl, rtol, atol, st);
-    if (nr_fn != nullptr) { norm_exchange(0, nseg); sc.gbuf = nr_buf; sc.gworld = nr_world; }
-    launch_step_controller(sc, st);
-  }
+  launch_error_norm(es, p.partial, nseg, p.ctrl, rtol, atol, st);
+  if (nr_fn != nullptr) { norm_exchange(0, nseg); sc.gbuf = nr_buf; sc.gworld = nr_world; }
+  launch_step_controller(sc, st);
   if (!aug) {
     EmitArgs ea;
     ea.ctrl = p.ctrl; ea.targets = p.targets; ea.y0 = p.Y; ea.y1 = p.Y1;

@@ -88,8 +88,7 @@ struct StemPlan {
 };
 
 bool stem_takes_w4(const node_stem_shape* sh) {
-  const char* e = getenv("NODE_TUNE_STEM_W4");       // 0: the stem's own gather-GEMM kernels for the last convolution too (A/B, tests)
-  if (e && atoi(e) == 0) return false;
+  if (env_int("NODE_TUNE_STEM_W4", 1) == 0) return false;       // 0: the stem's own gather-GEMM kernels for the last convolution too (A/B, tests)
   const int h2 = ((sh->h - 2 - 1) / 2 + 1 - 1) / 2 + 1, w2 = ((sh->w - 2 - 1) / 2 + 1 - 1) / 2 + 1;
   return h2 == 8 && w2 == 8 && sh->filters % 128 == 0 && sh->n % 8 == 0 && 16 % (sh->filters / 32) == 0;
 }

@@ -1,5 +1,5 @@
 // Decisions of the adaptive step loop, shared by the kernels that take them: k_step_controller / k_init_controller (one launch per
-// decision, kernels_pointwise.hip) and k_tiny_solve (a whole forward solve in one launch, kernels_tiny_solve.hip) -- one source, so
+// decision, kernels_step_control.hip) and k_tiny_solve (a whole forward solve in one launch, kernels_tiny_solve.hip) -- one source, so
 // the two step loops cannot drift apart.  `a.ctrl` may live in global memory or in LDS.
 #pragma once
 #include "node_internal.h"

@@ -21,7 +21,7 @@ static bool launch_w4_gemm_variant(const W4Switches&, const float*, const unsign
 #endif
 
 static W4Switches w4_read_switches() {
-  auto rd = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+  auto rd = env_int;
   W4Switches sw = {rd("NODE_TUNE_W4_GEMM64", 1), rd("NODE_TUNE_W4_BF16X3", 1), rd("NODE_TUNE_W4_SHAREV", 1), rd("NODE_TUNE_W4_GEMM128", -1),
                    rd("NODE_TUNE_W4_WGRAD128", -1), rd("NODE_TUNE_W4_F16", 1), rd("NODE_TUNE_W4_H256", 1), 0, nullptr};
   w4_diag_switches(sw);

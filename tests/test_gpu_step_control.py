@@ -3,7 +3,7 @@ tests/test_step_control_host.py pins to the oracle: k_lincomb, k_init_norms + k_
 k_emit_flat, k_commit, k_flat_scalar, k_flat_time, k_set_scalar_state -- driven through generic.FlatSolve (node_flat_*) on buffers
 filled with chosen data.  No dynamics function, no convolution.
 
-Sizes (csrc/kernels_pointwise.hip; every kernel runs 256 threads per workgroup):
+Sizes (csrc/kernels_step_control.hip; every kernel runs 256 threads per workgroup):
   * k_error_norm: grid ERR_BLOCKS = 512, one float4 per thread and sweep -> a sweep covers 512 * 256 * 4 = 524288 elements; the
     n % 4 tail is block 0's.  524288 + 5 = one float4 of a second sweep + a tail of one; 1027 = 256 float4 + a tail of three.
   * k_init_norms: grid 512, one ELEMENT per thread and sweep -> 131072 per sweep; 131072 + 1 starts the second.
