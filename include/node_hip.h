@@ -382,6 +382,28 @@ typedef struct node_sgd_tensor {
 int node_sgd_step(const node_sgd_tensor* tensors, int count, float lr, float momentum, float weight_decay,
                   float grad_scale, const float* skip_if_nonzero, void* stream);
 
+/* The reference's other optimizer -- train.py:138 (`Adam(params, lr, weight_decay=wd)`) -- in the same form: every parameter
+ * tensor in one update launch (per 64 tensors), torch.optim.Adam's arithmetic with amsgrad off and coupled L2 weight decay:
+ *   g = grad_scale * grad + weight_decay * p;  exp_avg += (1 - beta1) (g - exp_avg);  exp_avg_sq = beta2 exp_avg_sq + (1 - beta2) g g
+ *   t = step + 1;  p -= (lr / (1 - beta1^t)) * exp_avg / (sqrt(exp_avg_sq) / sqrt(1 - beta2^t) + eps)
+ * `step` is a one-element fp32 counter per tensor in DEVICE memory (PyTorch's state['step']), read by the update launch and
+ * advanced by one by a second, one-workgroup launch behind it; the bias corrections are formed in double from it.  exp_avg
+ * and exp_avg_sq start at zero, step at 0.  beta1 / beta2 are read as the shortest decimal d that rounds to the float given
+ * (0.999f means 0.999, the double a PyTorch caller holds): the kernel multiplies by (float)d and (float)(1 - d) and forms
+ * d^t in double.  1 - beta2 formed from the float's own value, 0.99900001287, would be off by 1.3e-5 of itself, and
+ * exp_avg_sq with it.  A float that is no short decimal is taken within half an ulp of its own value.  `skip_if_nonzero`
+ * as for node_sgd_step: a skipped step changes nothing and advances no counter. */
+typedef struct node_adam_tensor {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  float* step;
+  size_t n;
+} node_adam_tensor;
+int node_adam_step(const node_adam_tensor* tensors, int count, float lr, float beta1, float beta2, float eps,
+                   float weight_decay, float grad_scale, const float* skip_if_nonzero, void* stream);
+
 /* The residual stem in front of the ODE block -- model.py:167-178 (`ResDownsample`):
  *     nn.Conv2d(in_ch, 64, 3, 1)                                              bias, no padding
  *     ResBlock(64, 64,      stride=2, downsample=conv1x1(64, 64, 2))          model.py:284-310

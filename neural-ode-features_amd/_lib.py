@@ -32,7 +32,7 @@ EXPORTS = [
     'node_odefunc_fwd', 'node_odefunc_vjp', 'node_solve_fwd', 'node_solve_adjoint',
     'node_backprop_workspace_bytes', 'node_solve_backprop',
     'node_head_fwd', 'node_head_bwd', 'node_gn_relu_fwd', 'node_gn_relu_bwd',
-    'node_sgd_step', 'node_profile_begin', 'node_profile_end',
+    'node_sgd_step', 'node_adam_step', 'node_profile_begin', 'node_profile_end',
     'node_conv3x3_w4_workspace_bytes', 'node_conv3x3_w4', 'node_w4_split3', 'node_w4_pair_stats',
     'node_stem_workspace_bytes', 'node_stem_fwd', 'node_stem_bwd', 'node_stem_conv_workspace_bytes', 'node_stem_conv',
     'node_head_loss_scratch_bytes', 'node_head_loss_fwd', 'node_head_loss_bwd',
@@ -87,6 +87,11 @@ class NodeProfile(C.Structure):
 
 class NodeSgdTensor(C.Structure):
     _fields_ = [('param', C.c_void_p), ('grad', C.c_void_p), ('momentum_buf', C.c_void_p), ('n', C.c_size_t)]
+
+
+class NodeAdamTensor(C.Structure):
+    _fields_ = [('param', C.c_void_p), ('grad', C.c_void_p), ('exp_avg', C.c_void_p), ('exp_avg_sq', C.c_void_p),
+                ('step', C.c_void_p), ('n', C.c_size_t)]
 
 
 STEM_PARAM_FIELDS = ('conv0_w', 'conv0_b', 'b1_n1_w', 'b1_n1_b', 'b1_c1_w', 'b1_n2_w', 'b1_n2_b', 'b1_c2_w', 'b1_ds_w',
@@ -203,6 +208,8 @@ def load():
     lib.node_gn_relu_bwd.argtypes = [P(NodeShape), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp]
     lib.node_sgd_step.restype = i32
     lib.node_sgd_step.argtypes = [P(NodeSgdTensor), i32, f32, f32, f32, f32, vp, vp]
+    lib.node_adam_step.restype = i32
+    lib.node_adam_step.argtypes = [P(NodeAdamTensor), i32, f32, f32, f32, f32, f32, f32, vp, vp]
     lib.node_profile_begin.restype = i32
     lib.node_profile_begin.argtypes = []
     lib.node_profile_end.restype = i32

@@ -1,10 +1,25 @@
 // C ABI of what stands beside the solver: the F(4x4,3x3) diagnostics, GroupNorm + ReLU and the classifier head as
-// stand-alone layers, the SGD step.
+// stand-alone layers, the SGD and Adam steps.
 #include "solver.h"     // (g_w4_pair_stats)
 
+#include <cstdio>
+#include <cstdlib>
 #include <cstring>
 
 using namespace node;
+
+// The double a caller of a float argument meant: the shortest decimal that rounds to `b` (0.999f -> 0.999, the double
+// PyTorch works with).  node_adam_step needs it for 1 - beta: (double)0.999f is 0.99900001287, whose 1 - beta2 is off by
+// 1.3e-5 of its value -- and so would exp_avg_sq be, 200 fp32 ulps away from torch.optim.Adam's.
+static double shortest_decimal(float b) {
+  char text[32];
+  for (int digits = 1; digits <= 9; ++digits) {
+    snprintf(text, sizeof(text), "%.*g", digits, (double)b);
+    const double d = strtod(text, nullptr);
+    if ((float)d == b) return d;
+  }
+  return (double)b;
+}
 
 extern "C" {
 
@@ -156,6 +171,38 @@ int node_sgd_step(const node_sgd_tensor* tensors, int count, float lr, float mom
   }
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_sgd_step failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
+int node_adam_step(const node_adam_tensor* tensors, int count, float lr, float beta1, float beta2, float eps, float weight_decay,
+                   float grad_scale, const float* skip_if_nonzero, void* stream) {
+  if (count < 0) return fail(NODE_ERR_ARG, "count < 0");
+  if (count == 0) return NODE_OK;
+  if (!tensors) return fail(NODE_ERR_NULL, "tensors is NULL");
+  if (!(lr >= 0.f) || !(eps >= 0.f) || !(weight_decay >= 0.f)) return fail(NODE_ERR_ARG, "lr / eps / weight_decay must be >= 0");
+  if (!(beta1 >= 0.f && beta1 < 1.f) || !(beta2 >= 0.f && beta2 < 1.f)) return fail(NODE_ERR_ARG, "beta1 / beta2 must lie in [0, 1)");
+  for (int i = 0; i < count; ++i) {
+    const node_adam_tensor& t = tensors[i];
+    if (!t.param || !t.grad || !t.exp_avg || !t.exp_avg_sq || !t.step) return fail(NODE_ERR_NULL, "tensor %d: a pointer is NULL", i);
+    if ((((uintptr_t)t.param) | ((uintptr_t)t.grad) | ((uintptr_t)t.exp_avg) | ((uintptr_t)t.exp_avg_sq) | ((uintptr_t)t.step)) & 3)
+      return fail(NODE_ERR_ARG, "tensor %d: pointers must be 4-byte aligned", i);
+  }
+  const double b1 = shortest_decimal(beta1), b2 = shortest_decimal(beta2);
+  for (int base = 0; base < count; base += ADAM_TABLE) {
+    AdamTable tb;
+    memset(&tb, 0, sizeof(tb));
+    const int m = count - base < ADAM_TABLE ? count - base : ADAM_TABLE;
+    size_t max_n = 0;
+    for (int i = 0; i < m; ++i) {
+      const node_adam_tensor& t = tensors[base + i];
+      tb.e[i].p = t.param; tb.e[i].g = t.grad; tb.e[i].m = t.exp_avg; tb.e[i].v = t.exp_avg_sq; tb.e[i].step = t.step;
+      tb.e[i].n = t.n;
+      if (t.n > max_n) max_n = t.n;
+    }
+    launch_adam_multi(tb, m, max_n, lr, b1, b2, eps, weight_decay, grad_scale, skip_if_nonzero, (hipStream_t)stream);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_adam_step failed: %s", hipGetErrorString(e));
   return NODE_OK;
 }
 

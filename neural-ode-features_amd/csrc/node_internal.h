@@ -514,6 +514,12 @@ struct SgdEntry { float* p; const float* g; float* m; size_t n; };
 struct SgdTable { SgdEntry e[SGD_TABLE]; };
 void launch_sgd_multi(const SgdTable& tb, int count, size_t max_n, float lr, float momentum, float wd, float gscale,
                       const float* skip, hipStream_t s);
+// fused multi-tensor Adam (kernels_optim.hip): the update launch and, behind it, the one that advances the step counters
+constexpr int ADAM_TABLE = 64;      // 48 B per entry: 3 KiB of the 4 KiB of kernel arguments
+struct AdamEntry { float* p; const float* g; float* m; float* v; float* step; size_t n; };
+struct AdamTable { AdamEntry e[ADAM_TABLE]; };
+void launch_adam_multi(const AdamTable& tb, int count, size_t max_n, float lr, double b1, double b2, float eps, float wd,
+                       float gscale, const float* skip, hipStream_t s);
 void launch_head_bwd(const node_shape& sh, const float* z, const float* gamma, const float* beta, const float* scale,
                      const float* stats, const float* gpool, float* dz, float* gpart, hipStream_t s);
 

@@ -144,12 +144,13 @@ def train(data, model, optimizer, args, gen, loop=None, epoch=0):
 
 
 def deferred_loop(model, optimizer, args):
-    """--deferred: the training step as a closure for integrate.DeferredLoop (needs FusedSGD: its launch is the one
-    commit point the device flag predicates; one optimizer step per batch)."""
+    """--deferred: the training step as a closure for integrate.DeferredLoop (needs FusedSGD or FusedAdam: its launch is
+    the one commit point the device flag predicates; one optimizer step per batch)."""
     from . import integrate
-    from .optim import FusedSGD
-    if not isinstance(optimizer, FusedSGD) or args.batch_accumulation != 1 or not args.adjoint or args.method != 'dopri5':
-        raise SystemExit('--deferred needs -o sgd, --batch-accumulation 1, --adjoint and --method dopri5')
+    from .optim import FusedAdam, FusedSGD
+    if not isinstance(optimizer, (FusedSGD, FusedAdam)) or args.batch_accumulation != 1 or not args.adjoint or args.method != 'dopri5':
+        raise SystemExit('--deferred needs a fused optimizer (optim.FusedSGD or optim.FusedAdam: -o sgd / -o adam), '
+                         '--batch-accumulation 1, --adjoint and --method dopri5')
 
     def step(images, target):
         logits = model(images)
@@ -271,7 +272,7 @@ def main(argv=None):
     if args.optim == 'sgd':
         optimizer = nof.FusedSGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.wd)   # train.py:136
     else:
-        optimizer = torch.optim.Adam(model.parameters(), lr=args.lr, weight_decay=args.wd)           # train.py:138
+        optimizer = nof.FusedAdam(model.parameters(), lr=args.lr, weight_decay=args.wd)               # train.py:138
 
     if args.resume:
         ckpt = torch.load(last, map_location=args.device, weights_only=False)
