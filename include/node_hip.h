@@ -509,6 +509,32 @@ typedef struct node_augment {
 int node_augment_batch(const node_augment* aug, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
                        uint64_t seed, uint32_t epoch, float* out, int64_t* out_labels, void* stream);
 
+/* The 4x4 stride-2 padding-1 convolution that turns the image into the ODE block's state -- the whole of the one-shot stem,
+ * model.py:119-126 (`nn.Conv2d(in_ch, filters, 4, 2, 1)`), and the conv1 of the `ode` / `ode2` stems (model.py:185, 203):
+ *     y = conv2d(x, weight, bias, stride 2, padding 1)
+ * x: [n, in_ch, h, w] NCHW fp32 with 1 <= in_ch <= 4 and even h, w >= 4; weight: [filters, in_ch, 4, 4] with filters % 64 == 0;
+ * bias: [filters] or NULL; y / grad_y: [n, filters, h / 2, w / 2] NCHW fp32, the layout the solver consumes.  Anything else is
+ * refused with NODE_ERR_UNSUPPORTED.  All arithmetic is fp32 FMA (vector ALU), sums in a fixed order: no floating-point
+ * atomics, every result is bit-reproducible run to run.
+ *   node_imgconv_fwd  one launch.
+ *   node_imgconv_bwd  d_weight[o][c][kh][kw] = sum_{n,oh,ow} grad_y[n][o][oh][ow] x[n][c][2 oh - 1 + kh][2 ow - 1 + kw] and
+ *                     d_bias[o] = sum grad_y (NULL: not wanted) from ONE read of grad_y: per-slab partials in `ws`, summed in
+ *                     slab order by a second small launch.  d_x (NULL: not wanted, nothing is launched for it) is one more
+ *                     launch: each input pixel receives 2 x 2 taps x filters terms.  d_x must be 8-byte aligned.
+ * Gradients are written, not accumulated.  The workspace carries nothing between calls (the forward needs none), but two calls
+ * that may run at the same time (two streams) need a workspace each.  The calls never synchronise, allocate or read back.
+ * node_imgconv_fwd is captured into graphs by graphs.capture_inference; a capture of node_imgconv_bwd has not been run and
+ * is not claimed: imgconv.py keeps it out of captures.  filters <= 65536.  node_imgconv_workspace_bytes returns 0, with a
+ * message behind node_last_error(), for a shape it refuses. */
+typedef struct node_imgconv_shape {
+  int32_t n, in_ch, h, w, filters;
+} node_imgconv_shape;
+size_t node_imgconv_workspace_bytes(const node_imgconv_shape* shape);
+int node_imgconv_fwd(const node_imgconv_shape* shape, const float* x, const float* weight, const float* bias, float* y,
+                     void* stream);
+int node_imgconv_bwd(const node_imgconv_shape* shape, const float* x, const float* weight, const float* grad_y, float* d_weight,
+                     float* d_bias, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
 /* Event-based per-kernel-class timing (off by default; adds two event records
  * per profiled launch).  begin() resets the counters; end() synchronises the
  * recorded events and fills `out`. */

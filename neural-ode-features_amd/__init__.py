@@ -12,6 +12,7 @@ from .modules import ConcatConv2d, ODEBlock, ODEfunc, normalization  # noqa: F40
 from .odenet import FCClassifier, ODEDownsample, ODEDownsample2, ODENet, ResBlock, StackedODENet  # noqa: F401
 from . import augment, dp, graphs, optim, retrieval  # noqa: F401
 from .augment import Augmenter, DeviceSplit  # noqa: F401
+from .imgconv import ImageConv2d  # noqa: F401
 from .optim import FusedAdam, FusedSGD  # noqa: F401
 from .head import cross_entropy, linear, linear_cross_entropy  # noqa: F401
 

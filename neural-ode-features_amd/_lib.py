@@ -40,6 +40,7 @@ EXPORTS = [
     'node_flat_finish_step', 'node_flat_status_read',
     'node_retrieval_workspace_bytes', 'node_retrieval_ap', 'node_rank_ap',
     'node_augment_batch',
+    'node_imgconv_workspace_bytes', 'node_imgconv_fwd', 'node_imgconv_bwd',
 ]
 
 
@@ -146,6 +147,10 @@ AUG_CROP, AUG_JITTER, AUG_FLIP, AUG_NORM = 1, 2, 4, 8
 class NodeAugment(C.Structure):
     _fields_ = [('n', C.c_int32), ('c', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('padding', C.c_int32),
                 ('flags', C.c_uint32), ('saturation', C.c_float), ('hue', C.c_float), ('mean', C.c_float * 3), ('std', C.c_float * 3)]
+
+
+class NodeImgConvShape(C.Structure):
+    _fields_ = [('n', C.c_int32), ('in_ch', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('filters', C.c_int32)]
 
 
 class NodeHipError(RuntimeError):
@@ -260,6 +265,12 @@ def load():
     lib.node_rank_ap.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.node_augment_batch.restype = i32
     lib.node_augment_batch.argtypes = [P(NodeAugment), vp, vp, vp, i32, C.c_uint64, C.c_uint32, vp, vp, vp]
+    lib.node_imgconv_workspace_bytes.restype = sz
+    lib.node_imgconv_workspace_bytes.argtypes = [P(NodeImgConvShape)]
+    lib.node_imgconv_fwd.restype = i32
+    lib.node_imgconv_fwd.argtypes = [P(NodeImgConvShape), vp, vp, vp, vp, vp]
+    lib.node_imgconv_bwd.restype = i32
+    lib.node_imgconv_bwd.argtypes = [P(NodeImgConvShape), vp, vp, vp, vp, vp, vp, vp, sz, vp]
     ver = lib.node_abi_version()
     if ver != NODE_ABI_VERSION:
         raise RuntimeError('libnode_hip ABI %d != binding ABI %d' % (ver, NODE_ABI_VERSION))

@@ -542,4 +542,14 @@ struct AugmentArgs {
 void launch_augment(const AugmentArgs& a, int c, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
                     float* out, int64_t* out_labels, hipStream_t s);
 
+// the image convolution 4x4 / stride 2 / padding 1 in front of the ODE block (kernels_imgconv.hip; checks: imgconv_api.hip)
+constexpr int IMG_FWD_FILTERS = 32;    // filters per workgroup of the forward (filters % 64 == 0)
+constexpr int IMG_SLAB = 256;          // output pixels (flattened over n, oh, ow) per partial of the weight gradient
+struct ImgConvArgs { int n, h, w, oh, ow, filters, np; };      // np = n oh ow
+int imgconv_slabs(int64_t np);
+void launch_imgconv_fwd(const ImgConvArgs& a, int in_ch, const float* x, const float* w, const float* bias, float* y, hipStream_t s);
+void launch_imgconv_wgrad(const ImgConvArgs& a, int in_ch, const float* x, const float* dy, float* dw, float* db, float* ws,
+                          hipStream_t s);
+void launch_imgconv_dgrad(const ImgConvArgs& a, int in_ch, const float* w, const float* dy, float* dx, hipStream_t s);
+
 }  // namespace node

@@ -15,6 +15,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
+from .imgconv import ImageConv2d
 from .modules import ODEBlock, normalization
 
 
@@ -48,8 +49,8 @@ def _stem(kind, in_ch, out_ch, norm):
             nn.Conv2d(in_ch, 64, 3, 1),
             ResBlock(64, 64, stride=2, downsample=nn.Conv2d(64, 64, 1, 2, bias=False), norm=norm),
             ResBlock(64, out_ch, stride=2, downsample=nn.Conv2d(64, out_ch, 1, 2, bias=False), norm=norm))
-    if kind == 'one-shot':       # model.py:119-126
-        return nn.Conv2d(in_ch, out_ch, 4, 2, 1)
+    if kind == 'one-shot':       # model.py:119-126; forward / backward through the HIP library on a HIP device (imgconv.py)
+        return ImageConv2d(in_ch, out_ch, 4, 2, 1)
     if kind in ('convolution', 'minimal'):   # model.py:129-164
         mid = 64 if kind == 'convolution' else 24
         make_norm = normalization(norm)
@@ -66,7 +67,7 @@ class ODEDownsample(nn.Module):
 
     def __init__(self, in_ch, out_ch=64, method='dopri5', adjoint=False, t1=1, tol=1e-3, norm='group'):
         super().__init__()
-        self.conv1 = nn.Conv2d(in_ch, out_ch, 4, 2, 1)
+        self.conv1 = ImageConv2d(in_ch, out_ch, 4, 2, 1)
         self.odeblock = ODEBlock(n_filters=out_ch, adjoint=adjoint, t1=t1, tol=tol, method=method, norm=norm)
         self.maxpool = nn.MaxPool2d(4, 2, 1)
 
@@ -82,7 +83,7 @@ class ODEDownsample2(nn.Module):
 
     def __init__(self, in_ch, out_ch=64, method='dopri5', adjoint=False, t1=1, tol=1e-3, norm='group'):
         super().__init__()
-        self.conv1 = nn.Conv2d(in_ch, out_ch, 4, 2, 1)
+        self.conv1 = ImageConv2d(in_ch, out_ch, 4, 2, 1)
         self.odeblock = ODEBlock(n_filters=out_ch, adjoint=adjoint, t1=t1, tol=tol, method=method, norm=norm)
         self.norm = nn.Sequential(normalization(norm)(out_ch), nn.ReLU(inplace=True))
         self.conv2 = nn.Conv2d(out_ch, out_ch, 4, 2, 1)
