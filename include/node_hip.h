@@ -214,6 +214,23 @@ int node_w4_split3(const float* x, float* out, size_t n, void* stream);
  * cotangent exponent k too high, so that its first step overflows and is repeated. */
 int node_w4_pair_stats(int32_t* out4);
 
+/* Diagnostics (tests, tools; ABI 6): which kernel instances and which tiling the library selects for a shape in THIS process (the
+ * NODE_TUNE_* switches that move the geometry are read as the solver reads them), without touching a device.  The launchers switch on
+ * the same two values (csrc/kernels_wgrad.hip wgrad_kernel_for, csrc/conv_select.hip conv_kernel_for), so what this reports is what
+ * runs.  wgrad_kernel: the fp32 weight-gradient instance -- k_wgrad_w2<units of 8 | 4>, k_wgrad_w<W, RB>, k_wgrad_t<W, RB>, k_wgrad_p.
+ * conv_kernel: the fp32 3x3 convolution instance -- direct / 1-D Winograd at 64-, 128- or 256-row tiles, 2-D Winograd (128 rows).
+ * The other fields are the solver's Dims of the same names (csrc/node_internal.h); wino4 != 0 says that the F(4x4,3x3) pipeline
+ * (and, for c % 128 == 0, its own weight gradient) may serve the shape instead.  Returns the error the solver would give the shape. */
+enum { NODE_WGRAD_W2_8 = 0, NODE_WGRAD_W2_4, NODE_WGRAD_W_8_8, NODE_WGRAD_W_16_2, NODE_WGRAD_W_4_4,
+       NODE_WGRAD_T_8_8, NODE_WGRAD_T_16_4, NODE_WGRAD_T_7_7, NODE_WGRAD_T_4_4, NODE_WGRAD_P, NODE_WGRAD_KERNELS };
+enum { NODE_CONV_DIRECT_64 = 0, NODE_CONV_DIRECT_128, NODE_CONV_DIRECT_256, NODE_CONV_W1_64, NODE_CONV_W1_128, NODE_CONV_W1_256,
+       NODE_CONV_W2_128, NODE_CONV_KERNELS };
+typedef struct node_dims_info {
+  int32_t wgrad_kernel, conv_kernel;
+  int32_t wino, bm, s, csplit, mtiles, ntile, small, tiny, wino4, w4q, wgrad_wino, wut, rb, nbands, nsplit, wgrad_pair;
+} node_dims_info;
+int node_describe_dims(const node_shape* shape, node_dims_info* out);
+
 /* torchdiffeq.odeint(ODEfunc, y0, t, rtol, atol, method)  -- model.py:367
  * t_pts: host array of n_t strictly monotonic times; y_out: [n_t, n, c, h, w]
  * with y_out[0] = y0. */

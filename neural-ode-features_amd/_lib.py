@@ -29,6 +29,7 @@ ERRORS = {
 
 EXPORTS = [
     'node_abi_version', 'node_last_error', 'node_param_count', 'node_workspace_bytes', 'node_solve_is_resident',
+    'node_describe_dims',
     'node_odefunc_fwd', 'node_odefunc_vjp', 'node_solve_fwd', 'node_solve_adjoint',
     'node_backprop_workspace_bytes', 'node_solve_backprop',
     'node_head_fwd', 'node_head_bwd', 'node_gn_relu_fwd', 'node_gn_relu_bwd',
@@ -53,6 +54,28 @@ class NodeParams(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in (
         'norm1_w', 'norm1_b', 'conv1_w', 'conv1_b', 'norm2_w', 'norm2_b',
         'conv2_w', 'conv2_b', 'norm3_w', 'norm3_b')]
+
+
+# the kernel instances node_describe_dims names, in the order of the NODE_WGRAD_* / NODE_CONV_* enums of include/node_hip.h
+WGRAD_KERNELS = ('W2_8', 'W2_4', 'W_8_8', 'W_16_2', 'W_4_4', 'T_8_8', 'T_16_4', 'T_7_7', 'T_4_4', 'P')
+CONV_KERNELS = ('DIRECT_64', 'DIRECT_128', 'DIRECT_256', 'W1_64', 'W1_128', 'W1_256', 'W2_128')
+
+
+class NodeDimsInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in (
+        'wgrad_kernel', 'conv_kernel', 'wino', 'bm', 's', 'csplit', 'mtiles', 'ntile', 'small', 'tiny', 'wino4', 'w4q',
+        'wgrad_wino', 'wut', 'rb', 'nbands', 'nsplit', 'wgrad_pair')]
+
+
+def describe_dims(n, c, h, w, groups=None, eps=1e-5):
+    """What the library selects for an [n, c, h, w] state in this process: dict of node_dims_info with the two kernel instances by
+    name ('wgrad_kernel', 'conv_kernel').  Needs no GPU; raises NodeHipError for a shape the solver refuses."""
+    info = NodeDimsInfo()
+    check(load().node_describe_dims(C.byref(NodeShape(n, c, h, w, min(32, c) if groups is None else groups, eps)), C.byref(info)))
+    out = {k: getattr(info, k) for k, _ in info._fields_}
+    out['wgrad_kernel'] = WGRAD_KERNELS[info.wgrad_kernel]
+    out['conv_kernel'] = CONV_KERNELS[info.conv_kernel]
+    return out
 
 
 class NodeStats(C.Structure):
@@ -188,6 +211,8 @@ def load():
     lib.node_workspace_bytes.argtypes = [P(NodeShape), i32, i32, i32]
     lib.node_solve_is_resident.restype = i32
     lib.node_solve_is_resident.argtypes = [P(NodeShape)]
+    lib.node_describe_dims.restype = i32
+    lib.node_describe_dims.argtypes = [P(NodeShape), P(NodeDimsInfo)]
     lib.node_odefunc_fwd.restype = i32
     lib.node_odefunc_fwd.argtypes = [P(NodeShape), P(NodeParams), f32, vp, vp, vp, sz, vp]
     lib.node_odefunc_vjp.restype = i32

@@ -11,10 +11,21 @@ namespace node {
 int g_conv_bm = -1;
 int g_conv_wino = -1;
 
+// WHICH instance serves a geometry: a pure function of Dims.  node_describe_dims reports it; launch_conv and the families' launchers
+// switch on it, so the description cannot drift from what is launched.
+int conv_kernel_for(const Dims& d) {
+  if (d.wino == 2) return NODE_CONV_W2_128;   // (make_dims admits the 2-D kernel at 128-row tiles only)
+  if (d.wino) return d.BM == 64 ? NODE_CONV_W1_64 : d.BM == 128 ? NODE_CONV_W1_128 : NODE_CONV_W1_256;
+  return d.BM == 64 ? NODE_CONV_DIRECT_64 : d.BM == 128 ? NODE_CONV_DIRECT_128 : NODE_CONV_DIRECT_256;
+}
+
 void launch_conv(const Dims& d, const ConvArgs& a, hipStream_t s) {
-  if (d.wino == 2) launch_conv_w2(d, a, s);
-  else if (d.wino) launch_conv_w(d, a, s);
-  else launch_conv_direct(d, a, s);
+  const int k = conv_kernel_for(d);
+  switch (k) {
+    case NODE_CONV_W2_128: launch_conv_w2(d, a, s); return;
+    case NODE_CONV_W1_64: case NODE_CONV_W1_128: case NODE_CONV_W1_256: launch_conv_w(d, a, k, s); return;
+    default: launch_conv_direct(d, a, k, s); return;
+  }
 }
 
 size_t conv_lds_bytes(const Dims& d, int /*mode*/) { return d.wino == 2 ? conv_w2_lds_bytes(d) : d.wino ? conv_w_lds_bytes(d) : conv_direct_lds_bytes(d); }

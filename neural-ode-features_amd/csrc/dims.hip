@@ -169,4 +169,19 @@ int node_solve_is_resident(const node_shape* shape) {
   return d.tiny != 0 && tiny_resident_ok(d) ? 1 : 0;
 }
 
+int node_describe_dims(const node_shape* shape, node_dims_info* out) {
+  if (!out) return fail(NODE_ERR_NULL, "out is NULL");
+  memset(out, 0, sizeof(*out));
+  Dims d;
+  const int rc = dims_for(shape, &d);
+  if (rc != NODE_OK) return rc;
+  out->wgrad_kernel = wgrad_kernel_for(d, wgrad_variant());
+  out->conv_kernel = conv_kernel_for(d);
+  out->wino = d.wino; out->bm = d.BM; out->s = d.S; out->csplit = d.csplit; out->mtiles = d.mtiles; out->ntile = d.ntile;
+  out->small = d.small ? 1 : 0; out->tiny = d.tiny; out->wino4 = d.wino4; out->w4q = d.w4q;
+  out->wgrad_wino = d.wgrad_wino; out->wut = d.wut; out->rb = d.RB; out->nbands = d.nbands; out->nsplit = d.nsplit;
+  out->wgrad_pair = d.wgrad_pair;
+  return NODE_OK;
+}
+
 }  // extern "C"

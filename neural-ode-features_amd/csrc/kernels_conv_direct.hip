@@ -317,11 +317,11 @@ static void launch_conv_t(const Dims& d, const ConvArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((k_conv3x3<WM, MT>), dim3(d.mtiles, d.ntile), dim3(WM * 128), conv_direct_lds_bytes(d), s, a, d);
 }
 
-// d.BM (chosen by make_dims): 64 = four-wave workgroups, two of which share a CU and cover each other's
-// barriers / prologue / epilogue when the grid is small; 128 / 256 = eight waves.
-void launch_conv_direct(const Dims& d, const ConvArgs& a, hipStream_t s) {
-  if (d.BM == 64) launch_conv_t<2, 1>(d, a, s);
-  else if (d.BM == 128) launch_conv_t<4, 1>(d, a, s);   // (four waves x (64 x 32) per wave measured slower: 94 vs 91 us at cfg 2)
+// kernel = conv_kernel_for(d), which follows d.BM (chosen by make_dims): 64 = four-wave workgroups, two of which share a CU and
+// cover each other's barriers / prologue / epilogue when the grid is small; 128 / 256 = eight waves.
+void launch_conv_direct(const Dims& d, const ConvArgs& a, int kernel, hipStream_t s) {
+  if (kernel == NODE_CONV_DIRECT_64) launch_conv_t<2, 1>(d, a, s);
+  else if (kernel == NODE_CONV_DIRECT_128) launch_conv_t<4, 1>(d, a, s);   // (four waves x (64 x 32) per wave measured slower: 94 vs 91 us at cfg 2)
   else launch_conv_t<4, 2>(d, a, s);
 }
 

@@ -398,10 +398,10 @@ static void launch_conv_w_t(const Dims& d, const ConvArgs& a, hipStream_t s) {
   hipLaunchKernelGGL((k_conv3x3_w<MT>), dim3(d.mtiles, d.ntile), dim3(512), conv_w_lds_bytes(d), s, a, d);
 }
 
-// 1-D Winograd along the rows (even W); weights packed by launch_pack_weights_w
-void launch_conv_w(const Dims& d, const ConvArgs& a, hipStream_t s) {
-  if (d.BM == 64) launch_conv_w_t<1>(d, a, s);
-  else if (d.BM == 128) launch_conv_w_t<2>(d, a, s);
+// 1-D Winograd along the rows (even W); weights packed by launch_pack_weights_w; kernel = conv_kernel_for(d)
+void launch_conv_w(const Dims& d, const ConvArgs& a, int kernel, hipStream_t s) {
+  if (kernel == NODE_CONV_W1_64) launch_conv_w_t<1>(d, a, s);
+  else if (kernel == NODE_CONV_W1_128) launch_conv_w_t<2>(d, a, s);
   else launch_conv_w_t<4>(d, a, s);
 }
 

@@ -886,27 +886,45 @@ static void launch_wgrad_t(const Dims& d, const WgradArgs& a, dim3 grid, size_t 
   hipLaunchKernelGGL((k_wgrad_t<W, RB>), grid, dim3(WG_THREADS), lds, s, a, d);
 }
 
+// WHICH instance serves a geometry (a pure function of Dims and the variant switch; node_describe_dims reports it and
+// launch_wgrad switches on it, so the two cannot disagree).
 // variant 1 (production): templated kernel where the geometry has an instance, generic otherwise;
-// variant 0: always the generic kernel.
+// variant 0: always the generic kernel behind the Winograd-domain ones.
+int wgrad_kernel_for(const Dims& d, int variant) {
+  if (d.wgrad_wino == 2) {   // 2-D Winograd domain (make_dims sets wut)
+    if (d.wut == 8) return NODE_WGRAD_W2_8;
+    if (d.wut == 4) return NODE_WGRAD_W2_4;
+  }
+  if (d.wgrad_wino == 1) {   // 1-D Winograd-domain accumulation, ordinary nine-tap slabs (make_dims sets RB)
+    if (d.W == 8 && d.RB == 8) return NODE_WGRAD_W_8_8;
+    if (d.W == 16 && d.RB == 2) return NODE_WGRAD_W_16_2;
+    if (d.W == 4 && d.RB == 4) return NODE_WGRAD_W_4_4;
+  }
+  if (variant >= 1 && d.H % d.RB == 0) {
+    if (d.W == 8 && d.RB == 8) return NODE_WGRAD_T_8_8;
+    if (d.W == 16 && d.RB == 4) return NODE_WGRAD_T_16_4;
+    if (d.W == 7 && d.RB == 7) return NODE_WGRAD_T_7_7;
+    if (d.W == 4 && d.RB == 4) return NODE_WGRAD_T_4_4;
+  }
+  return NODE_WGRAD_P;
+}
+
 void launch_wgrad(const Dims& d, const WgradArgs& a, hipStream_t s) {
   const int ntc = (d.C + 63) / 64;
   const dim3 grid(ntc * ntc, d.nsplit);
+  const dim3 grid2(ntc * ntc, d.nsplit, a.act2 != nullptr ? 2 : 1);
   const size_t lds = wgrad_lds_bytes(d);
-  if (d.wgrad_wino == 2) {   // 2-D Winograd domain (make_dims sets wut)
-    const dim3 grid2(ntc * ntc, d.nsplit, a.act2 != nullptr ? 2 : 1);
-    if (d.wut == 8) { launch_wgrad_w2<8>(d, a, grid2, s); return; }
-    if (d.wut == 4) { launch_wgrad_w2<4>(d, a, grid2, s); return; }
-  }
-  if (d.wgrad_wino == 1) {   // 1-D Winograd-domain accumulation, ordinary nine-tap slabs (make_dims sets RB)
-    if (d.W == 8 && d.RB == 8) { launch_wgrad_w<8, 8>(d, a, grid, s); return; }
-    if (d.W == 16 && d.RB == 2) { launch_wgrad_w<16, 2>(d, a, grid, s); return; }
-    if (d.W == 4 && d.RB == 4) { launch_wgrad_w<4, 4>(d, a, grid, s); return; }
-  }
-  if (wgrad_variant() >= 1 && d.H % d.RB == 0) {
-    if (d.W == 8 && d.RB == 8) { launch_wgrad_t<8, 8>(d, a, grid, lds, s); return; }
-    if (d.W == 16 && d.RB == 4) { launch_wgrad_t<16, 4>(d, a, grid, lds, s); return; }
-    if (d.W == 7 && d.RB == 7) { launch_wgrad_t<7, 7>(d, a, grid, lds, s); return; }
-    if (d.W == 4 && d.RB == 4) { launch_wgrad_t<4, 4>(d, a, grid, lds, s); return; }
+  switch (wgrad_kernel_for(d, wgrad_variant())) {
+    case NODE_WGRAD_W2_8: launch_wgrad_w2<8>(d, a, grid2, s); return;
+    case NODE_WGRAD_W2_4: launch_wgrad_w2<4>(d, a, grid2, s); return;
+    case NODE_WGRAD_W_8_8: launch_wgrad_w<8, 8>(d, a, grid, s); return;
+    case NODE_WGRAD_W_16_2: launch_wgrad_w<16, 2>(d, a, grid, s); return;
+    case NODE_WGRAD_W_4_4: launch_wgrad_w<4, 4>(d, a, grid, s); return;
+    case NODE_WGRAD_T_8_8: launch_wgrad_t<8, 8>(d, a, grid, lds, s); return;
+    case NODE_WGRAD_T_16_4: launch_wgrad_t<16, 4>(d, a, grid, lds, s); return;
+    case NODE_WGRAD_T_7_7: launch_wgrad_t<7, 7>(d, a, grid, lds, s); return;
+    case NODE_WGRAD_T_4_4: launch_wgrad_t<4, 4>(d, a, grid, lds, s); return;
+    default: break;
   }
   static bool attr[MAX_DEVICES];
   allow_full_lds((const void*)k_wgrad_p, attr);

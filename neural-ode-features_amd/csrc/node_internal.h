@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <cstdlib>
+#include "../../include/node_hip.h"   // NODE_WGRAD_* / NODE_CONV_*: the kernel instances the selectors name
 
 namespace node {
 
@@ -394,10 +395,12 @@ struct ConvArgs {
   unsigned long long* stamps;  // diagnostics only (NODE_STAMPS builds); nullptr otherwise
   int ablate;                  // diagnostics only (NODE_STAMPS builds): timing-only ablation bits
 };
-void launch_conv(const Dims& d, const ConvArgs& a, hipStream_t s);    // conv_select.hip: the kernel family Dims::wino names
-// the families behind it (kernels_conv_{direct,wino1d,wino2d}.hip): launcher (Dims::BM picks the instantiation) and LDS bytes of a launch
-void launch_conv_direct(const Dims& d, const ConvArgs& a, hipStream_t s);
-void launch_conv_w(const Dims& d, const ConvArgs& a, hipStream_t s);
+int conv_kernel_for(const Dims& d);                                   // conv_select.hip: the instance (NODE_CONV_* of node_hip.h) a geometry selects
+void launch_conv(const Dims& d, const ConvArgs& a, hipStream_t s);    // conv_select.hip: launches that instance
+// the families behind it (kernels_conv_{direct,wino1d,wino2d}.hip): launcher (kernel = conv_kernel_for(d) picks the instantiation) and LDS
+// bytes of a launch
+void launch_conv_direct(const Dims& d, const ConvArgs& a, int kernel, hipStream_t s);
+void launch_conv_w(const Dims& d, const ConvArgs& a, int kernel, hipStream_t s);
 void launch_conv_w2(const Dims& d, const ConvArgs& a, hipStream_t s);
 size_t conv_direct_lds_bytes(const Dims& d);
 size_t conv_w_lds_bytes(const Dims& d);
@@ -429,7 +432,9 @@ struct WgradArgs {
   const float* dz2;
   float* wpart2;
 };
-void launch_wgrad(const Dims& d, const WgradArgs& a, hipStream_t s);
+int wgrad_variant();                                  // NODE_TUNE_WGRAD_VARIANT / g_wgrad_variant
+int wgrad_kernel_for(const Dims& d, int variant);     // the instance (NODE_WGRAD_* of node_hip.h) a geometry selects
+void launch_wgrad(const Dims& d, const WgradArgs& a, hipStream_t s);   // launches that instance
 size_t wgrad_lds_bytes(const Dims& d);
 
 struct ThetaFinalizeArgs {

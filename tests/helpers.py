@@ -89,6 +89,136 @@ def per_sample_err(a, b):
     return (a - b).abs().flatten(1).amax(dim=1) / (b.abs().max() + 1e-30)
 
 
+# ----------------------------------------------------------------------------------------------------------------------
+# The parameter gradient block by block (tests/test_param_blocks_host.py, tests/test_gpu_param_grads.py).
+#
+# rel_err over the flat vector of all 18 C^2 + 26 C gradients is one max-norm divided by the largest of them; the ten tensors
+# differ in scale (the time-channel taps and the first GroupNorm's bias are ~1e-2 of the largest under the kink-free set), so
+# a bound of 5e-5 on the flat vector is a bound of half a percent on those.  The blocks below are each compared at their OWN scale.
+# ----------------------------------------------------------------------------------------------------------------------
+TAPS = [(kh, kw) for kh in range(3) for kw in range(3)]
+
+
+def param_grad_blocks(flat_or_dict, C):
+    """The named blocks of a parameter gradient: the six GroupNorm vectors, the two conv biases and, for each conv weight
+    [C][1 + C][3][3], the time-channel block `w[:, 0]` ('convK.w_t', [C, 3, 3]) and the nine data-tap blocks `w[:, 1:, kh, kw]`
+    ('convK.tap<kh><kw>', [C, C]).  Takes the flat vector in parameters() order (what odefunc_vjp returns) or a mapping keyed
+    like PARAM_ORDER; returns an ordered dict of fp64 CPU tensors."""
+    if isinstance(flat_or_dict, dict):
+        parts = {k: flat_or_dict[k].detach().double().cpu() for k in PARAM_ORDER}
+    else:
+        flat = flat_or_dict.detach().double().cpu().reshape(-1)
+        assert flat.numel() == 18 * C * C + 26 * C, (flat.numel(), C)
+        parts, o = {}, 0
+        for k in PARAM_ORDER:
+            n = 9 * C * (C + 1) if k.endswith('_layer.weight') else C
+            parts[k] = flat[o:o + n]
+            o += n
+    out = {}
+    for k in PARAM_ORDER:
+        if k.endswith('_layer.weight'):
+            w = parts[k].reshape(C, C + 1, 3, 3)
+            name = k.split('.')[0]
+            out[name + '.w_t'] = w[:, 0]
+            for kh, kw in TAPS:
+                out['%s.tap%d%d' % (name, kh, kw)] = w[:, 1:, kh, kw]
+        elif k.endswith('_layer.bias'):
+            out[k.split('.')[0] + '.bias'] = parts[k].reshape(C)
+        else:
+            out[k] = parts[k].reshape(C)
+    return out
+
+
+def block_scales(ref64, scales=None):
+    """The scale of every block: max |ref64| over the block, unless `scales` names another one (the conv biases and vjp_t, whose
+    true values are cancelled sums: odefunc_vjp_ref64)."""
+    out = {k: float(v.abs().max()) for k, v in ref64.items()}
+    out.update(scales or {})
+    return out
+
+
+def block_errors(got, ref64, scales=None):
+    """max |got - ref64| / scale(block) for every block of ref64 (mappings of name -> tensor, param_grad_blocks's plus any scalar
+    the caller adds, such as 'vjp_t')."""
+    sc = block_scales(ref64, scales)
+    errs = {}
+    for k, r in ref64.items():
+        g = torch.as_tensor(got[k]).detach().double().cpu().reshape(r.shape)
+        errs[k] = float((g - r).abs().max()) / (sc[k] + 1e-300)
+    return errs
+
+
+def odefunc_vjp_ref64(t, y, params, cot, eps=1e-5):
+    """The fp64 reference of one VJP of the dynamics: `oracle.dynamics.odefunc_forward` restated op by op in float64 on the CPU
+    (nothing of the package is involved), with the two conv outputs kept so that their cotangents can be read.  `t` is rounded
+    to fp32 first (the number every fp32 implementation is given).  Returns dict(f, vy, vt, vp (flat, parameters() order),
+    blocks (param_grad_blocks of vp plus 'vjp_t'), scales): `scales` holds the blocks whose true value is a cancelled sum --
+      * the conv biases: max_co sum_{n,h,w} |dL/d(conv output)|.  With one channel per group the GroupNorm behind the conv removes
+        the bias exactly and the true gradient is identically zero; every implementation's value is the rounding of that sum;
+      * vjp_t = sum_layers sum_{co,tap} W[co,0,tap] dL/dW[co,0,tap] / t: the sum of the terms' magnitudes."""
+    from oracle.dynamics import concat_conv2d, n_groups
+    t32 = float(torch.tensor(float(t), dtype=torch.float32))
+    tt = torch.tensor(t32, dtype=torch.float64, requires_grad=True)
+    x = y.detach().double().cpu().clone().requires_grad_(True)
+    p = {k: params[k].detach().double().cpu().clone().requires_grad_(True) for k in PARAM_ORDER}
+    g = n_groups(x.shape[1])
+    C = x.shape[1]
+    a1 = F.relu(F.group_norm(x, g, p['norm1.weight'], p['norm1.bias'], eps))
+    c1 = concat_conv2d(tt, a1, p['conv1._layer.weight'], p['conv1._layer.bias'])
+    c1.retain_grad()
+    a2 = F.relu(F.group_norm(c1, g, p['norm2.weight'], p['norm2.bias'], eps))
+    c2 = concat_conv2d(tt, a2, p['conv2._layer.weight'], p['conv2._layer.bias'])
+    c2.retain_grad()
+    f = F.group_norm(c2, g, p['norm3.weight'], p['norm3.bias'], eps)
+    f.backward(cot.detach().double().cpu())
+    grads = {k: v.grad for k, v in p.items()}
+    blocks = param_grad_blocks(grads, C)
+    blocks['vjp_t'] = tt.grad.detach().reshape(1)
+    scales = {'conv1.bias': float(c1.grad.abs().sum(dim=(0, 2, 3)).max()), 'conv2.bias': float(c2.grad.abs().sum(dim=(0, 2, 3)).max())}
+    vt_terms = sum(float((p[k][:, 0].detach() * grads[k][:, 0]).abs().sum()) for k in ('conv1._layer.weight', 'conv2._layer.weight'))
+    scales['vjp_t'] = vt_terms / abs(t32)
+    return dict(f=f.detach(), vy=x.grad, vt=float(tt.grad), vp=torch.cat([grads[k].reshape(-1) for k in PARAM_ORDER]),
+                blocks=blocks, scales=scales)
+
+
+def vjp_block_errors(vp, vt, ref):
+    """block_errors of a VJP's (flat parameter gradient, vjp_t) against odefunc_vjp_ref64's result."""
+    C = ref['f'].shape[1]
+    got = param_grad_blocks(vp, C)
+    got['vjp_t'] = torch.as_tensor(float(vt), dtype=torch.float64).reshape(1)
+    return block_errors(got, ref['blocks'], ref['scales'])
+
+
+def block_table(title, errs, ref, bound):
+    """The per-block table of one case as text: error relative to the block's scale, the scale, and the scale relative to the
+    largest gradient of the flat vector."""
+    sc = block_scales(ref['blocks'], ref['scales'])
+    gmax = float(ref['vp'].abs().max())
+    lines = ['%s  (block bound %.1e)' % (title, bound)]
+    for k, e in errs.items():
+        lines.append('  %-14s err %.2e  scale %.3e  scale/max|vp| %.2e%s' % (k, e, sc[k], sc[k] / gmax, '' if e <= bound else '  <-- MISS'))
+    return '\n'.join(lines)
+
+
+def emit_table(text):
+    """Print a case's table; NODE_PARAM_GRAD_TABLES=<file> also appends it there (how profiles/param_grad_blocks.txt is made)."""
+    print(text, flush=True)
+    path = os.environ.get('NODE_PARAM_GRAD_TABLES')
+    if path:
+        with open(path, 'a') as fh:
+            fh.write(text + '\n')
+
+
+def assert_param_blocks(title, ref, vp, vt, bound):
+    """Every block of (vp, vt) within `bound` of odefunc_vjp_ref64's result `ref`, relative to the block's own scale; prints the
+    per-block table first."""
+    errs = vjp_block_errors(vp, vt, ref)
+    emit_table(block_table(title, errs, ref, bound))
+    over = {k: e for k, e in errs.items() if not e <= bound}
+    assert not over, (title, over)
+    return errs
+
+
 _F64_DEVICE = None
 
 

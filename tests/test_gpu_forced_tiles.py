@@ -3,7 +3,9 @@
 The tiling heuristic serves small batches with 64-pixel tiles (1-D Winograd kernel), so the regular parity
 shapes reach `k_conv3x3_w2` only at full size.  This test forces 128-pixel tiles (NODE_TUNE_CONV_BM=128, read
 once per process, hence the child process) and checks forward and VJP against the oracle on shapes that
-exercise ragged last tiles, 4x4 and 4x8 images (8 and 4 samples per tile), two K chunks and six."""
+exercise ragged last tiles, 4x4 and 4x8 images (8 and 4 samples per tile), two K chunks and six.  The child asserts through
+`node_describe_dims` that every shape does select that kernel (the rows of tests/param_grad_cases.py FORCED_W2), and holds the
+parameter gradient to the fp64 oracle block by block as well (tests/helpers.py)."""
 import os
 import subprocess
 import sys
@@ -15,12 +17,16 @@ pytestmark = pytest.mark.gpu
 CHILD = r'''
 import sys, torch
 sys.path.insert(0, sys.argv[1])
-from tests.helpers import make_func, rel_err
+from tests.helpers import assert_param_blocks, make_func, odefunc_vjp_ref64, rel_err
+from tests import param_grad_cases as cases
 import neural_ode_features_amd as nof
 from oracle.dynamics import odefunc_vjp as oracle_vjp
 bad = 0
+cases.assert_group_environment(cases.FORCED_W2[0])
+rows = {r['shape']: r for r in cases.FORCED_W2[2]}
 for shape in [(5, 64, 8, 8), (16, 32, 4, 4), (3, 32, 4, 8), (7, 96, 8, 8), (33, 64, 8, 8)]:
     N, C, H, W = shape
+    assert cases.assert_selection(rows[shape])['conv_kernel'] == 'W2_128'
     f, twin = make_func(C, seed=C + H, device='cuda', kink_free=True)
     gen = torch.Generator().manual_seed(5)
     y = torch.randn(N, C, H, W, generator=gen)
@@ -31,6 +37,11 @@ for shape in [(5, 64, 8, 8), (16, 32, 4, 4), (3, 32, 4, 8), (7, 96, 8, 8), (33, 
     print(shape, errs)
     if not (errs[0] < 2e-5 and errs[1] < 5e-5 and errs[2] < 5e-5):
         bad += 1
+    try:
+        assert_param_blocks('forced 2-D Winograd conv %s' % (shape,), odefunc_vjp_ref64(0.41, y, dict(twin.named_parameters()), cot), vp, vt, 5e-5)
+    except AssertionError as e:
+        print('MISS', e)
+        bad += 1
 sys.exit(bad)
 '''
 
@@ -39,6 +50,7 @@ def test_2d_winograd_conv_on_small_batches():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, NODE_TUNE_CONV_BM='128', NODE_TUNE_CONV_WINO='2')
     r = subprocess.run([sys.executable, '-c', CHILD, root], env=env, capture_output=True, text=True, timeout=600)
+    print(r.stdout)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
 
 

@@ -2,24 +2,27 @@
 import pytest
 import torch
 
-from tests.helpers import make_func, rel_err
+from tests.helpers import assert_param_blocks, make_func, odefunc_vjp_ref64, rel_err
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [  # (N, C, H, W)
-    (2, 8, 7, 7),       # 1 channel / group, odd image, C < one K chunk
-    (3, 16, 5, 6),      # non-square
-    (2, 64, 8, 8),      # MNIST-like width, 2 ch / group
-    (5, 64, 7, 7),      # MNIST config state (49 px: 2 samples per 128-row tile, ragged last tile)
-    (4, 96, 4, 4),      # 3 ch / group: N tile of 63 columns
-    (3, 256, 8, 8),     # CIFAR width
-    (2, 32, 16, 16),    # 256-row tiles (one sample per tile); Winograd conv MT=4, Winograd wgrad <16, 2>
-    (2, 32, 6, 6),      # even width, odd number of column pairs: Winograd conv, direct wgrad
-    (3, 64, 4, 4),      # Winograd wgrad <4, 4>, four samples per 64-pixel tile (ragged: 3)
-    (2, 32, 12, 12),    # HW = 144: 256-pixel tile with one sample; wgrad falls back to the generic kernel
-    (2, 16, 10, 14),    # non-square, even width 14 (7 column pairs)
-    (130, 64, 8, 8),    # 130 tiles of 64 pixels, Winograd wgrad <8, 8>, split-K over 65 units per slab
-]
+# (N, C, H, W) -> the (weight-gradient, convolution) kernel instances the shape selects, as node_describe_dims reports them
+# (_lib.WGRAD_KERNELS / _lib.CONV_KERNELS); test_odefunc_vjp_matches_oracle asserts them, so they cannot go stale
+SELECTS = {
+    (2, 8, 7, 7): ('T_7_7', 'DIRECT_64'),       # 1 channel / group, odd image, C < one K chunk
+    (3, 16, 5, 6): ('P', 'W1_64'),              # non-square
+    (2, 64, 8, 8): ('W2_8', 'W1_64'),           # MNIST-like width, 2 ch / group
+    (5, 64, 7, 7): ('T_7_7', 'DIRECT_64'),      # MNIST config state (49 px: one sample per 64-row tile)
+    (4, 96, 4, 4): ('W2_4', 'W1_64'),           # 3 ch / group: N tile of 63 columns
+    (3, 256, 8, 8): ('W2_8', 'W1_64'),          # CIFAR width
+    (2, 32, 16, 16): ('W2_8', 'W2_128'),        # 256 pixels: the conv in two 128-row bands per sample
+    (2, 32, 6, 6): ('P', 'W1_64'),              # even width, odd number of column pairs
+    (3, 64, 4, 4): ('W2_4', 'W1_64'),           # three samples in one 64-row tile
+    (2, 32, 12, 12): ('P', 'W1_256'),           # HW = 144: 256-row tile with one sample
+    (2, 16, 10, 14): ('P', 'W1_256'),           # non-square, even width 14 (7 column pairs)
+    (130, 64, 8, 8): ('W2_8', 'W1_64'),         # 130 tiles of 64 pixels; 260 units of 8 Winograd tiles over 32 K splits
+}
+SHAPES = list(SELECTS)
 # Shapes with >= 10^5 elements use the kink-free parameter set (tests/helpers.py:make_func): with ordinary
 # parameters one pre-activation of this very input lands within fp32 rounding of a ReLU kink and the oracle and
 # the GPU disagree on ONE element of vjp_y by 5 % (measured; 0 elements with kink-free parameters).
@@ -45,6 +48,7 @@ def test_odefunc_forward_matches_oracle(shape):
 @pytest.mark.parametrize('shape', SHAPES)
 def test_odefunc_vjp_matches_oracle(shape):
     import neural_ode_features_amd as nof
+    from neural_ode_features_amd import _lib
     from oracle.dynamics import odefunc_vjp as oracle_vjp
     N, C, H, W = shape
     f, twin = make_func(C, seed=C + H, device='cuda', kink_free=shape in KINK_FREE)
@@ -52,6 +56,8 @@ def test_odefunc_vjp_matches_oracle(shape):
     y = torch.randn(N, C, H, W, generator=gen)
     cot = torch.randn(N, C, H, W, generator=gen)
     t = -0.61
+    d = _lib.describe_dims(N, C, H, W)
+    assert (d['wgrad_kernel'], d['conv_kernel']) == SELECTS[shape], d
     fo, vy, vt, vp = nof.odefunc_vjp(f, t, y.cuda(), cot.cuda())
     p = dict(twin.named_parameters())
     f_ref, vy_ref, vt_ref, vp_ref = oracle_vjp(t, y, p, cot)
@@ -59,6 +65,8 @@ def test_odefunc_vjp_matches_oracle(shape):
                 vt=abs(float(vt) - float(vt_ref)) / (abs(float(vt_ref)) + 1e-6))
     print('vjp', shape, errs)
     assert errs['f'] < 2e-5 and errs['vy'] < 5e-5 and errs['vp'] < 5e-5 and errs['vt'] < 1e-4, errs
+    # ... and every block of the parameter gradient at its OWN scale, against fp64 (tests/helpers.py)
+    assert_param_blocks('parity %s' % (shape,), odefunc_vjp_ref64(t, y, p, cot), vp, vt, 5e-5)
 
 
 def test_vjp_t_is_deterministic_over_repeated_launches():

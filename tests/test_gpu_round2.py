@@ -19,7 +19,7 @@ import torch.nn.functional as F
 
 from oracle import torchdiffeq_restated as tdq
 from oracle.dynamics import odefunc_vjp as oracle_vjp
-from tests.helpers import _arbiter_device, make_func, per_sample_err, rel_err, robust_grad_err
+from tests.helpers import _arbiter_device, assert_param_blocks, make_func, odefunc_vjp_ref64, per_sample_err, rel_err, robust_grad_err
 
 pytestmark = pytest.mark.gpu
 
@@ -302,6 +302,8 @@ def test_16x16_split_conv_forward_and_vjp(shape):
           'vjp_t', float(vt), float(vt_ref))
     assert rel_err(fo, f_ref) < 2e-5 and rel_err(vy, vy_ref) < 5e-5 and rel_err(vp, vp_ref) < 5e-5
     assert abs(float(vt) - float(vt_ref)) < 1e-4 * abs(float(vt_ref)) + 1e-3
+    # ... and every block of the parameter gradient at its own scale, against fp64 (tests/helpers.py)
+    assert_param_blocks('16x16 %s' % (shape,), odefunc_vjp_ref64(0.4, y, dict(twin.named_parameters()), cot), vp, vt, 5e-5)
     assert rel_err(nof.odefunc_forward(f, 0.4, y.cuda()), f_ref) < 2e-5
     # ordinary parameters: forward tight, the ReLU-mask path of the backward per sample
     f, twin = make_func(C, seed=63, device='cuda')
@@ -330,6 +332,8 @@ def test_32x32_states_forward_and_vjp(shape):
           'vjp_t', float(vt), float(vt_ref))
     assert rel_err(fo, f_ref) < 3e-5 and rel_err(vy, vy_ref) < 1e-4 and rel_err(vp, vp_ref) < 1e-4
     assert abs(float(vt) - float(vt_ref)) < 1e-4 * abs(float(vt_ref)) + 1e-3
+    # ... and every block of the parameter gradient at its own scale, against fp64 (an fp32 path: 5e-5)
+    assert_param_blocks('32x32 %s' % (shape,), odefunc_vjp_ref64(0.4, y, dict(twin.named_parameters()), cot), vp, vt, 5e-5)
     assert rel_err(nof.odefunc_forward(f, 0.4, y.cuda()), f_ref) < 3e-5
 
 

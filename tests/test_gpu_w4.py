@@ -10,7 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import make_func, rel_err, oracle_vjp
+from tests.helpers import assert_param_blocks, make_func, odefunc_vjp_ref64, rel_err, oracle_vjp
 
 pytestmark = pytest.mark.gpu
 
@@ -208,6 +208,8 @@ def test_w4_odefunc_forward_and_vjp_match_oracle(shape):
                 vjp_t=abs(float(vt) - float(ref_vt)) / max(1.0, abs(float(ref_vt))))
     print('F(4x4,3x3) vs oracle at', shape, {k: '%.2e' % v for k, v in errs.items()})
     assert errs['f'] < 3e-5 and errs['vjp_y'] < 1e-4 and errs['vjp_params'] < 1e-4 and errs['vjp_t'] < 1e-4, errs
+    # ... and every block of the parameter gradient at its own scale, against fp64
+    assert_param_blocks('F(4x4,3x3) %s' % (shape,), odefunc_vjp_ref64(0.3, y, dict(twin.named_parameters()), cot), vp, vt, 1e-4)
 
 
 @pytest.mark.parametrize('shape', [(128, 256, 8, 8), (12, 256, 8, 8), (4, 256, 16, 16), (3, 256, 16, 16)])
@@ -221,17 +223,21 @@ def test_w4_wgrad128_matches_oracle(shape):
     y = torch.randn(N, Cc, H, W, generator=gen)
     cot = torch.randn(N, Cc, H, W, generator=gen)
     _, _, _, ref_vp = oracle_vjp(torch.tensor(0.3), y, dict(twin.named_parameters()), cot)
-    got = {}
+    got, got_vt = {}, {}
     for mode in ('0', '1'):
         os.environ['NODE_TUNE_W4_WGRAD128'] = mode
         try:
             with wino4(2):
-                got[mode] = integrate.odefunc_vjp(f, 0.3, y.cuda(), cot.cuda())[3]
+                _, _, got_vt[mode], got[mode] = integrate.odefunc_vjp(f, 0.3, y.cuda(), cot.cuda())
         finally:
             del os.environ['NODE_TUNE_W4_WGRAD128']
     e0, e1 = rel_err(got['0'], ref_vp), rel_err(got['1'], ref_vp)
     print('weight gradient vs oracle at', shape, 'k_w4_wgrad %.2e, k_w4_wgrad128b %.2e, between them %.2e' % (e0, e1, rel_err(got['1'], got['0'])))
     assert e0 < 1e-4 and e1 < 1e-4 and e1 < 2 * e0 + 1e-6
+    # ... and every block of both kernels' gradients at its own scale, against fp64
+    ref = odefunc_vjp_ref64(0.3, y, dict(twin.named_parameters()), cot)
+    for mode, name in (('0', 'k_w4_wgrad'), ('1', 'k_w4_wgrad128b')):
+        assert_param_blocks('%s %s' % (name, shape), ref, got[mode], got_vt[mode], 1e-4)
 
 
 @pytest.mark.parametrize('tol,gain,side', [(1e-3, 1.0, 8), (1e-5, 1.0, 8), (1e-5, 4.0, 8), (1e-5, 12.0, 8), (1e-3, 1.0, 16), (1e-5, 4.0, 16)])

@@ -17,7 +17,7 @@ def test_library_exports_every_declared_symbol():
     from neural_ode_features_amd import _lib
     header = open(os.path.join(ROOT, 'include', 'node_hip.h')).read()
     declared = set(re.findall(r'\b(node_[a-z_0-9]+)\s*\(', header))
-    declared -= {'node_shape', 'node_params', 'node_stats', 'node_solve_opts', 'node_profile'}
+    declared -= {'node_shape', 'node_params', 'node_stats', 'node_solve_opts', 'node_profile', 'node_dims_info'}
     assert declared == set(_lib.EXPORTS), (declared ^ set(_lib.EXPORTS))
     lib = _lib.load()
     for name in declared:
@@ -270,8 +270,13 @@ def test_header_is_plain_c_and_ctypes_layouts_match(tmp_path):
         'node_flat_seg': (_lib.NodeFlatSeg, ['y', 'y1', 'k', 'n']),
         'node_flat_solve': (_lib.NodeFlatSolve, ['nseg', 'has_scalar', 'seg', 'rtol', 'atol', 'tsign', 'n_targets', 'ws', 'ws_bytes']),
         'node_flat_status': (_lib.NodeFlatStatus, ['done', 'status', 'steps', 'accepted', 'rejected', 't', 'dt', 'first_dt', 'scalar']),
+        'node_dims_info': (_lib.NodeDimsInfo, [k for k, _ in _lib.NodeDimsInfo._fields_]),
     }
+    # the kernel instances node_describe_dims names: the binding's tuples follow the header's enums value by value
+    enums = (['NODE_WGRAD_' + k for k in _lib.WGRAD_KERNELS] + ['NODE_WGRAD_KERNELS'] +
+             ['NODE_CONV_' + k for k in _lib.CONV_KERNELS] + ['NODE_CONV_KERNELS'])
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "node_hip.h"', 'int main(void) {']
+    lines += ['  printf("%s %%d\\n", (int)%s);' % (e, e) for e in enums]
     for name, (_, fields) in structs.items():
         lines.append('  printf("%s %%zu\\n", sizeof(%s));' % (name, name))
         for f in fields:
@@ -286,6 +291,9 @@ def test_header_is_plain_c_and_ctypes_layouts_match(tmp_path):
         assert int(got[name]) == C.sizeof(ct), name
         for f in fields:
             assert int(got['%s.%s' % (name, f)]) == getattr(ct, f).offset, (name, f)
+    assert C.sizeof(_lib.NodeDimsInfo) == 4 * len(_lib.NodeDimsInfo._fields_) == 72
+    want = list(range(len(_lib.WGRAD_KERNELS) + 1)) + list(range(len(_lib.CONV_KERNELS) + 1))
+    assert [int(got[e]) for e in enums] == want, [(e, got[e]) for e in enums]
 
 
 def test_optimizer_and_training_loop_refuse_the_cpu():
