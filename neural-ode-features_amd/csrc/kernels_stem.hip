@@ -5,13 +5,16 @@
 // and PyTorch reductions around the library's kernels.  Here the stem is NHWC from its first kernel to its last:
 //   k_stem_conv      forward convolutions and data gradients of the 64 / 256-channel layers: a gather GEMM over
 //                    (tap, input channel) on the bf16 matrix pipe at fp32 accuracy -- both operands arrive as exact bf16
-//                    triples, staged global -> LDS by plain 16-B copies, six v_mfma_f32_32x32x16_bf16 per fp32 product block
-//   k_stem_wgrad     weight gradients: the reduction runs over pixels, the lanes over channels, so NHWC rows are the
-//                    MFMA operands as they lie in memory (v_mfma_f32_32x32x2_f32, no LDS in the loop), split-K slabs
+//                    triples, staged global -> LDS by plain 16-B copies (LDS-DMA through a ring of stages), six
+//                    v_mfma_f32_32x32x16_bf16 per fp32 product block
+//   k_stem_wgrad     weight gradients on the same pipe and triples: the reduction runs over pixels, so the [pixel][channel]
+//                    rows go through the same LDS ring as they lie in memory and come out transposed
+//                    (ds_read_b64_tr_b16); split-K slabs
 //   k_stem_conv0_*   the first layer (K = 9 in_ch <= 27) on the NCHW input
 //   k_stem_gn_*      GroupNorm + ReLU forward (writes the triples the next convolution reads) and backward
 //   k_stem_prep / k_stem_from_nchw / k_stem_to_nchw / k_stem_reduce   filter splits, boundary layouts, slab sums
 #include "stem.h"
+#include <type_traits>
 
 namespace node {
 
@@ -52,32 +55,87 @@ __device__ __forceinline__ void split8(const float4& p, const float4& q, u32x4& 
 __device__ __forceinline__ float bf16_f(bf16_t v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
 
 // ============================================================================
-// LDS images of the two MFMA kernels below: [row][64 channels] bf16 = 128-B rows, one image per bf16 part, filled by
-// LDS-DMA (global_load_lds_dwordx4: one wave instruction = 1 KB = eight whole rows; the destination is lane-linear, so the
-// XOR swizzle sits on the per-lane SOURCE address): 16-B piece p of row r lives at slot p ^ ((r >> 1) & 7).  Both the
-// row reads (ds_read_b128, forward / data gradient) and the transposed reads (ds_read_b64_tr_b16, weight gradient) of a
-// 32-lane half then touch every bank once.
+// LDS images of the two MFMA kernels below: [row][KC channels] bf16, one image per bf16 part, filled by LDS-DMA
+// (global_load_lds_dwordx4: one wave instruction = 1 KB = 64 / PP whole rows of PP 16-B pieces; the destination is
+// lane-linear, so the XOR swizzle sits on the per-lane SOURCE address).  128-B rows (KC = 64): piece p of row r lives at
+// slot p ^ ((r >> 1) & 7); 64-B rows (KC = 32): at slot p ^ ((r >> 2) & 3).  Both the row reads (ds_read_b128, forward /
+// data gradient) and the transposed reads (ds_read_b64_tr_b16, weight gradient) of a 16-lane group then touch every bank once.
+//
+// Operand ring (both kernels): NST = D + 1 stages, D of them in flight.  The DMA pieces are inline asm: the compiler
+// neither knows of them nor drains them in front of an LDS read; the only ordering is, per K step q,
+//     s_waitcnt vmcnt(pieces of the stages issued behind stage q)   this wave's pieces of stage q have landed
+//     s_waitcnt lgkmcnt(0)                                          this wave's reads of stage q - 1 are in registers
+//     s_barrier                                                     ... and so have every other wave's
+//     issue stage q + D  into the slot of stage q - 1;  read and multiply stage q
+// (a stage is read one barrier behind the wait that retires it, and refilled one barrier behind its last read).
+// D = 1 is the double-buffered one-step schedule (vmcnt(0) + barrier per step); NODE_TUNE_STEM_RING=0 selects it per call.
 // ============================================================================
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 typedef short s16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ int img_off(int row, int piece) { return row * 128 + ((piece ^ ((row >> 1) & 7)) << 4); }
-// eight rows (row0 .. row0 + 7) of one image: lane L brings piece (L & 7) ^ swizzle of row row0 + (L >> 3)
-__device__ __forceinline__ void glds16(const bf16_t* src, unsigned char* lds_dst) {
-  __builtin_amdgcn_global_load_lds(reinterpret_cast<const void*>(src), (lds_ptr_t)lds_dst, 16, 0, 0);
+constexpr int STEM_RING_D = 3;
+template <int KC>
+__device__ __forceinline__ int img_off(int row, int piece) {
+  constexpr int PP = KC / 8, SH = KC == 64 ? 1 : 2;
+  return row * (2 * KC) + ((piece ^ ((row >> SH) & (PP - 1))) << 4);
+}
+// 64 / PP rows of one image: lane L brings its 16 bytes to lds_dst + 16 L (M0 is restored inside the statement)
+__device__ __forceinline__ void glds16(const bf16_t* src, unsigned lds_dst) {
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(src), "s"(lds_dst) : "memory");
+}
+template <int N>
+__device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
+// all but the pieces of the `ahead` (<= K) youngest stages have landed; NP pieces per stage and wave
+template <int NP, int K>
+__device__ __forceinline__ void wait_stages(int ahead) {
+  if constexpr (K == 0) {
+    wait_vm<0>();
+  } else {
+    if (ahead >= K) wait_vm<K * NP>();
+    else wait_stages<NP, K - 1>(ahead);
+  }
+}
+// the six part products of one fp32 product block, smallest first; `between` runs behind every pair (the LDS-DMA pieces of the
+// stage being refilled go there: a piece issued between MFMAs costs the wave its issue slot only, nine pieces in a row in
+// front of the MFMAs stall it for longer than the MFMAs take)
+template <class F>
+__device__ __forceinline__ void six_products(f32x16& acc, const bf16x8 (&x)[3], const bf16x8 (&y)[3], F&& between) {
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[2], y[0], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[2], acc, 0, 0, 0);
+  between();
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[1], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[1], y[0], acc, 0, 0, 0);
+  between();
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[1], acc, 0, 0, 0);
+  acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(x[0], y[0], acc, 0, 0, 0);
+  between();
+}
+// top of K step q of nq: stage q is complete and the slot of stage q - 1 is free when this returns
+template <int NP, int D>
+__device__ __forceinline__ void ring_step(int q, int nq) {
+  wait_stages<NP, D - 1>(min(q + D - 1, nq - 1) - q);
+  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_barrier();
+  asm volatile("" ::: "memory");
 }
 
 // ============================================================================
-// k_stem_conv: out[row][co] = sum_{tap, ci} in[row @ tap][ci] * w[tap][co][ci]
+// k_stem_conv<KC, D>: out[row][co] = sum_{tap, ci} in[row @ tap][ci] * w[tap][co][ci]
 //   tile: 128 rows x 64 columns, four waves, wave w = rows 32 w .. 32 w + 31 x both 32-column blocks
-//   K chunk: one tap x 64 input channels = four MFMA K steps of six part products; both operands double-buffered in LDS
-//   (2 x 72 KB), chunk q + 1 in flight (LDS-DMA) while chunk q is multiplied, one barrier per chunk
-//   a lane stages the same four A rows for every chunk (row -> pixel decode once); a tap outside the image reads the zero row
+//   K chunk: one tap x KC input channels = KC / 16 MFMA K steps of six part products; both operands through the ring above
+//   (KC = 32: four stages of 36 KB, three in flight; KC = 64: two of 72 KB), one barrier per chunk
+//   a lane stages the same A rows for every chunk (row -> pixel decode once, source rows once per tap); a tap outside the
+//   image reads the zero row
 // ============================================================================
+template <int KC, int D>
 __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
-  constexpr int BM = 128, BN = 64;
-  constexpr int A_PLANE = BM * 128, B_PLANE = BN * 128, A_BYTES = 3 * A_PLANE, BUF = A_BYTES + 3 * B_PLANE;
+  constexpr int BM = 128, BN = 64, NST = D + 1, KS = KC / 16;
+  constexpr int ROWB = 2 * KC, PP = KC / 8, RPI = 64 / PP, SH = KC == 64 ? 1 : 2;
+  constexpr int A_PLANE = BM * ROWB, B_PLANE = BN * ROWB, A_BYTES = 3 * A_PLANE, BUF = A_BYTES + 3 * B_PLANE;
+  constexpr int NJA = 32 / RPI, NJB = 16 / RPI, NP = 3 * (NJA + NJB);   // DMA pieces per wave: 32 A rows, 16 B rows, three parts
   extern __shared__ __align__(16) unsigned char smem[];
-  int* out_off = reinterpret_cast<int*>(smem + 2 * BUF);
+  int* out_off = reinterpret_cast<int*>(smem + NST * BUF);
   const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
   const int ntn = a.Cout / BN;
   int b = blockIdx.x;
@@ -105,13 +163,13 @@ __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
   const bool extra_k = a.mode == 1 && a.in2 != nullptr && cpy == 0 && cpx == 0 && a.step == 2;
   const int row0 = (tile_m - tile0) * BM;
   const int Mc = a.N * ch * cw;
-  // the four A rows this lane stages: 32 wave + 8 j + lane / 8
-  const int lrow = lane >> 3, lslot = lane & 7;
-  int rn[4], roy[4], rox[4];
-  bool rval[4];
+  // the NJA A rows this lane stages: 32 wave + RPI j + lane / PP
+  const int lrow = lane / PP, lslot = lane & (PP - 1);
+  int rn[NJA], roy[NJA], rox[NJA];
+  bool rval[NJA];
 #pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const int rl = 32 * wave + 8 * j + lrow, r = row0 + rl;
+  for (int j = 0; j < NJA; ++j) {
+    const int rl = 32 * wave + RPI * j + lrow, r = row0 + rl;
     rval[j] = r < Mc;
     rn[j] = roy[j] = rox[j] = 0;
     if (rval[j]) {
@@ -123,25 +181,27 @@ __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
     }
     if (lslot == 0) out_off[rl] = rval[j] ? (rn[j] * a.OH + roy[j]) * a.OW + rox[j] : -1;
   }
-  const int ncc = a.Cin >> 6;
-  const int nmain = ntap * ncc;
-  const int nchunk = nmain + (extra_k ? ncc : 0);
+  const int ncc = a.Cin / KC;
+  const int nseg = ntap + (extra_k ? 1 : 0);       // K segments: the class' taps, then the shortcut's of a data gradient
+  const int nchunk = nseg * ncc;
 
-  auto issue = [&](int q, int buf) {
-    unsigned char* A = smem + buf * BUF;
-    unsigned char* B = A + A_BYTES;
-    const bool xk = q >= nmain;                      // the shortcut's segment of a data gradient
-    const int qq = xk ? q - nmain : q;
-    const int ti = qq / ncc, c0 = (qq - ti * ncc) << 6;
-    const int tap = xk ? 0 : (int)((taps >> (4 * ti)) & 15);
-    const int ky = xk ? 0 : tap / a.KW, kx = xk ? 0 : tap - ky * a.KW;
+  // the chunk the next issue() brings: (segment i_seg, channel chunk i_cc); per segment, the lane's sources at channel 0
+  int i_seg = 0, i_cc = 0;
+  const bf16_t* asrc[NJA];
+  const bf16_t* bsrc[NJB];
+  size_t a_pl = 0, b_pl = 0;
+  auto set_segment = [&]() {
+    const bool xk = i_seg >= ntap;                   // the shortcut's segment of a data gradient
+    const int tap = xk ? 0 : (int)((taps >> (4 * i_seg)) & 15);
+    const int ky = tap / a.KW, kx = tap - ky * a.KW;
     const int pad = xk ? 0 : a.pad;
     const bf16_t* in = xk ? a.in2 : a.in;
     const bf16_t* wq = xk ? a.w2 : wsel;
-    const size_t wq_plane = xk ? a.w2_plane : wsel_plane;
     const int wtap = (xk || wtaps_one) ? 0 : tap;
+    a_pl = a.in_plane;
+    b_pl = xk ? a.w2_plane : wsel_plane;
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < NJA; ++j) {
       int iy, ix;
       bool ok = rval[j];
       if (a.mode == 0) {
@@ -155,17 +215,28 @@ __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
       }
       ok = ok && (unsigned)iy < (unsigned)a.IH && (unsigned)ix < (unsigned)a.IW;
       const int irow = ok ? (rn[j] * a.IH + iy) * a.IW + ix : a.zero_row;
-      const int rl = 32 * wave + 8 * j + lrow;
-      const bf16_t* src = in + (size_t)irow * a.Cin + c0 + ((lslot ^ ((rl >> 1) & 7)) << 3);
-#pragma unroll
-      for (int p = 0; p < 3; ++p) glds16(src + p * a.in_plane, A + p * A_PLANE + (32 * wave + 8 * j) * 128);
+      const int rl = 32 * wave + RPI * j + lrow;
+      asrc[j] = in + (size_t)irow * a.Cin + ((lslot ^ ((rl >> SH) & (PP - 1))) << 3);
     }
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int col = 16 * wave + 8 * j + lrow;
-      const bf16_t* ws = wq + ((size_t)wtap * a.Cout + tile_n * BN + col) * a.Cin + c0 + ((lslot ^ ((col >> 1) & 7)) << 3);
-#pragma unroll
-      for (int p = 0; p < 3; ++p) glds16(ws + p * wq_plane, B + p * B_PLANE + (16 * wave + 8 * j) * 128);
+    for (int j = 0; j < NJB; ++j) {
+      const int col = 16 * wave + RPI * j + lrow;
+      bsrc[j] = wq + ((size_t)wtap * a.Cout + tile_n * BN + col) * a.Cin + ((lslot ^ ((col >> SH) & (PP - 1))) << 3);
+    }
+  };
+  const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem;
+  // piece k of NP of the chunk (i_seg, i_cc) into ring slot `stage`: A rows first (row group j, part p), then B
+  auto piece = [&](int k, int stage) {
+    const bool isb = k >= 3 * NJA;
+    const int kk = isb ? k - 3 * NJA : k, j = kk / 3, p = kk - 3 * j;
+    const int c0 = i_cc * KC;
+    if (!isb) glds16(asrc[j] + p * a_pl + c0, lds0 + stage * BUF + 32 * wave * ROWB + p * A_PLANE + j * RPI * ROWB);
+    else glds16(bsrc[j] + p * b_pl + c0, lds0 + stage * BUF + A_BYTES + 16 * wave * ROWB + p * B_PLANE + j * RPI * ROWB);
+  };
+  auto next_chunk = [&]() {
+    if (++i_cc == ncc) {
+      i_cc = 0;
+      if (++i_seg < nseg) set_segment();
     }
   };
 
@@ -175,77 +246,133 @@ __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc[c][i] = 0.f;
 
-  issue(0, 0);
+  set_segment();
+#pragma unroll
+  for (int q = 0; q < D; ++q)
+    if (q < nchunk) {
+#pragma unroll
+      for (int k = 0; k < NP; ++k) piece(k, q);
+      next_chunk();
+    }
   const int li = lane & 31, lg = lane >> 5;
   const int arow = 32 * wave + li;
-  for (int q = 0; q < nchunk; ++q) {
-    __syncthreads();                 // chunk q has landed (the barrier's fence drains the LDS-DMA); buffer (q + 1) & 1 is free
-    if (q + 1 < nchunk) issue(q + 1, (q + 1) & 1);
-    const unsigned char* A = smem + (q & 1) * BUF;
+  int st_read = 0, st_fill = D;                      // ring slots of stage q and of stage q + D
+  // one K step; FILL: stage q + D is requested, two MFMAs between its pieces
+  auto step = [&](int q, auto fill) {
+    constexpr bool FILL = decltype(fill)::value;
+    ring_step<NP, D>(q, nchunk);
+    const unsigned char* A = smem + st_read * BUF;
     const unsigned char* B = A + A_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks) {
-      bf16x8 fa[3];
+    // the fragments of K step ks + 1 are requested before the products of step ks issue
+    bf16x8 fa[2][3], fb[2][2][3];
+    auto fetch = [&](int ks, int s) {
 #pragma unroll
       for (int p = 0; p < 3; ++p)
-        fa[p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(A + p * A_PLANE + img_off(arow, 2 * ks + lg)));
+        fa[s][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(A + p * A_PLANE + img_off<KC>(arow, 2 * ks + lg)));
 #pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const int brow = 32 * c + li;
-        bf16x8 fb[3];
+      for (int c = 0; c < 2; ++c)
 #pragma unroll
         for (int p = 0; p < 3; ++p)
-          fb[p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(B + p * B_PLANE + img_off(brow, 2 * ks + lg)));
-        // smallest products first
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], acc[c], 0, 0, 0);
-        acc[c] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[c], 0, 0, 0);
+          fb[s][c][p] = __builtin_bit_cast(bf16x8, *reinterpret_cast<const u32x4*>(B + p * B_PLANE + img_off<KC>(32 * c + li, 2 * ks + lg)));
+    };
+    int pk = 0;
+    auto between = [&]() {
+      if constexpr (FILL) {
+        if (pk < NP) piece(pk, st_fill);
+        ++pk;
+        __builtin_amdgcn_sched_barrier(0);
       }
+    };
+    fetch(0, 0);
+#pragma unroll
+    for (int ks = 0; ks < KS; ++ks) {
+      const int s = ks & 1;
+      if (ks + 1 < KS) fetch(ks + 1, s ^ 1);
+      if constexpr (FILL) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int c = 0; c < 2; ++c) six_products(acc[c], fa[s], fb[s][c], between);
     }
-  }
+    static_assert(NP <= 6 * KS, "a chunk's pieces go between its MFMA pairs");
+    if constexpr (FILL) next_chunk();
+    st_read = st_read + 1 == NST ? 0 : st_read + 1;
+    st_fill = st_fill + 1 == NST ? 0 : st_fill + 1;
+  };
+  int q = 0;
+  for (; q + D < nchunk; ++q) step(q, std::true_type());
+  for (; q < nchunk; ++q) step(q, std::false_type());
 
-  // epilogue: register r of a 32 x 32 block = row 8 (r / 4) + 4 (lane / 32) + r % 4, column lane % 32: 128-B row stores
+  // epilogue: register r of a 32 x 32 block = row 8 (r / 4) + 4 (lane / 32) + r % 4, column lane % 32: 128-B row stores.
+  // The conditions are decided once; every load of a lane is requested before the first is used (a row past the end reads
+  // row 0 and stores nothing); the additions keep their order: acc + bias, + res, + out.
+  int off[16];
 #pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    const int col = tile_n * BN + 32 * c + li;
-    const float bv = a.bias ? a.bias[col] : 0.f;
+  for (int i = 0; i < 16; ++i) off[i] = out_off[32 * wave + 8 * (i >> 2) + 4 * lg + (i & 3)];
+  const int col0 = tile_n * BN + li;
+  if (shortcut_tile) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int rl = 32 * wave + 8 * (i >> 2) + 4 * lg + (i & 3);
-      const int off = out_off[rl];
-      if (off < 0) continue;
-      const size_t o = (size_t)off * a.Cout + col;
-      if (shortcut_tile) { a.out2[o] = acc[c][i]; continue; }
-      float v = acc[c][i] + bv;
-      if (a.res) v += a.res[o];
-      if (a.accumulate) v += a.out[o];
-      a.out[o] = v;
-    }
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i)
+        if (off[i] >= 0) a.out2[(size_t)off[i] * a.Cout + col0 + 32 * c] = acc[c][i];
+    return;
+  }
+  const float bv[2] = {a.bias ? a.bias[col0] : 0.f, a.bias ? a.bias[col0 + 32] : 0.f};
+  auto finish = [&](auto has_res, auto has_out) {
+    constexpr bool RES = decltype(has_res)::value, OUT = decltype(has_out)::value;
+    float r[2][16], o[2][16];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const size_t e = (size_t)max(off[i], 0) * a.Cout + col0 + 32 * c;
+        if constexpr (RES) r[c][i] = a.res[e];
+        if constexpr (OUT) o[c][i] = a.out[e];
+      }
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        float v = acc[c][i] + bv[c];
+        if constexpr (RES) v += r[c][i];
+        if constexpr (OUT) v += o[c][i];
+        if (off[i] >= 0) a.out[(size_t)off[i] * a.Cout + col0 + 32 * c] = v;
+      }
+  };
+  typedef std::true_type yes;
+  typedef std::false_type no;
+  if (a.res) {
+    if (a.accumulate) finish(yes(), yes());
+    else finish(yes(), no());
+  } else {
+    if (a.accumulate) finish(no(), yes());
+    else finish(no(), no());
   }
 }
 
 // ============================================================================
-// k_stem_wgrad<TG, EXTRA>: dW[tap][co][ci] = sum_pixels dy[pixel][co] * in[pixel @ tap][ci] on the bf16 matrix pipe at fp32
+// k_stem_wgrad<TG, EXTRA, D>: dW[tap][co][ci] = sum_pixels dy[pixel][co] * in[pixel @ tap][ci] on the bf16 matrix pipe at fp32
 //   accuracy.  Both operands are triples that already exist (the data gradient reads dy, the forward conv read `in`).
 //   The reduction runs over PIXELS, so an MFMA operand is eight consecutive pixels of one channel: the [pixel][channel]
 //   LDS images above, read with ds_read_b64_tr_b16 (a 4-row x 16-column block delivered column-major: the transpose is free).
 //   workgroup = (64 co x 64 ci tile, one kernel row ky = TG taps, one share of the pixels); wave w = the 32 x 32 block
 //   (w / 2, w % 2) for the TG taps; K chunk = 16 pixels = ONE MFMA K step: a dy image (6 KB) + TG gathered input images,
-//   double-buffered, filled by LDS-DMA while the previous chunk is multiplied.  Every workgroup writes its TG blocks of
-//   one slab; k_stem_reduce sums the slabs.
+//   through the ring above (D + 1 stages, D in flight).  Every workgroup writes its TG blocks of one slab; k_stem_reduce
+//   sums the slabs.
 //   EXTRA (ky == 1 only): the shortcut's 1x1 stride-s filter reads the pixel the centre tap reads -- one more accumulator,
 //   fed by the centre tap's input image and a second dy image.
+//   The body is compiled per wave (W) and per kind of workgroup (EX): which (image, part, half) pieces a wave brings, and how
+//   many, are constants -- no role branches in the loop, and the counted waits are immediates.
 // ============================================================================
-template <int TG, bool EXTRA>
-__global__ __launch_bounds__(256) void k_stem_wgrad(const SWgradArgs a) {
+template <int TG, bool EX, int D, int W>
+__device__ __forceinline__ void stem_wgrad_wave(const SWgradArgs& a, unsigned char* smem) {
+  constexpr int NST = D + 1;
   constexpr int IMG = 3 * 16 * 128;                 // one image: three parts x 16 pixels x 128 B
-  constexpr int NIMG = 1 + TG + (EXTRA ? 1 : 0);    // dy, TG inputs, dy2
+  constexpr int NIMG = 1 + TG + (EX ? 1 : 0);       // dy, TG inputs, dy2
   constexpr int BUF = NIMG * IMG;
-  extern __shared__ __align__(16) unsigned char smem[];
-  const int t = threadIdx.x, lane = t & 63, wave = __builtin_amdgcn_readfirstlane(t >> 6);
+  constexpr int NINST = NIMG * 6;                   // pieces of a stage: (image, part, half), dealt to the waves in turn:
+  constexpr int NP = (NINST - W + 3) / 4;           // wave W brings pieces W, W + 4, ... -- all of the half W & 1
+  constexpr int H = W & 1;
+  const int lane = threadIdx.x & 63;
   const int nct = a.Cin >> 6, npair = nct * (a.Cout >> 6);
   const int ngrp = TG == 3 ? 3 : 1;
   int bb = blockIdx.x;
@@ -253,59 +380,60 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const SWgradArgs a) {
   const int ky = bb % ngrp;
   const int split = bb / ngrp;
   const int cot = pair / nct, cit = pair - cot * nct;
-  const bool extra = EXTRA && ky == 1;
   const int rows = a.N * a.OH * a.OW;
   const int rbeg = split * a.rows_per_split;
   const int rend = min(rbeg + a.rows_per_split, rows);
   const int nchunk = rbeg < rend ? (rend - rbeg + 15) >> 4 : 0;
 
-  // staging: one wave instruction = 8 pixel rows of one part of one image; lane -> pixel row lane / 8 (+ 8 for the second
-  // half of the chunk), piece (lane & 7) ^ swizzle.  The pixel coordinates of both rows advance by 16 per chunk.
-  const int lrow = lane >> 3, lslot = lane & 7;
-  int pn[2], py[2], px[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int r = rbeg + 8 * h + lrow;
-    pn[h] = r / (a.OH * a.OW);
-    const int rem = r - pn[h] * a.OH * a.OW;
-    py[h] = rem / a.OW;
-    px[h] = rem - py[h] * a.OW;
+  // staging: one piece = 8 pixel rows of one part of one image; lane -> pixel row 8 H + lane / 8 of the chunk, 16-B piece
+  // (lane & 7) ^ swizzle.  The lane's pixel (py, px), its source row at tap (ky, 0) and its dy row advance by 16 pixels per
+  // chunk: 16 = an OH OW + ay OW + ax with at most one carry per digit, so the step is a handful of adds and selects.
+  const int rl = 8 * H + (lane >> 3);
+  const int sw = ((lane & 7) ^ ((rl >> 1) & 7)) << 3;
+  const int ohw = a.OH * a.OW;
+  const int an = 16 / ohw, ay = (16 - an * ohw) / a.OW, ax = 16 - an * ohw - ay * a.OW;
+  const int d_irow = (an * a.IH + ay * a.stride) * a.IW + ax * a.stride;
+  const int cx_irow = (a.IW - a.OW) * a.stride, cy_irow = (a.IH - a.OH * a.stride) * a.IW;
+  int r = rbeg + rl;                                 // the dy row
+  int py, px, irow;
+  {
+    const int pn = r / ohw, rem = r - pn * ohw;
+    py = rem / a.OW;
+    px = rem - py * a.OW;
+    irow = (pn * a.IH + py * a.stride - a.pad + (TG == 3 ? ky : 0)) * a.IW + px * a.stride - a.pad;
   }
-  auto issue = [&](int q, int buf) {
-    unsigned char* base = smem + buf * BUF;
-    const int r0 = rbeg + 16 * q;
-    constexpr int NINST = NIMG * 6;      // (image, part, half)
+  const bf16_t* dyb = a.dy3 + cot * 64 + sw;
+  const bf16_t* dy2b = EX ? a.dy23 + cot * 64 + sw : nullptr;
+  const bf16_t* inb = a.in + cit * 64 + sw;
+  const unsigned lds0 = (unsigned)(size_t)(lds_ptr_t)smem;
+  // source offsets of the chunk the lane's pixel stands at, then the pixel's step to the next chunk
+  size_t dyo, ino[TG];
+  auto sources = [&]() {
+    const bool valid = r < rend;
+    const int iy = py * a.stride - a.pad + (TG == 3 ? ky : 0), ix0 = px * a.stride - a.pad;
+    const bool oky = valid && (unsigned)iy < (unsigned)a.IH;
+    dyo = (size_t)(valid ? r : a.dy_zero_row) * a.Cout;
 #pragma unroll
-    for (int ii = 0; ii < (NINST + 3) / 4; ++ii) {
-      const int inst = wave + 4 * ii;
-      if (inst >= NINST) break;
-      const int im = inst / 6, part = (inst % 6) >> 1, h = inst & 1;
-      if (EXTRA && !extra && im == NIMG - 1) continue;
-      const int rl = 8 * h + lrow;
-      const bool valid = r0 + rl < rend;
-      const int sw = (lslot ^ ((rl >> 1) & 7)) << 3;
-      const bf16_t* src;
-      if (im == 0 || (EXTRA && im == NIMG - 1)) {
-        const bf16_t* d = im == 0 ? a.dy3 : a.dy23;
-        src = d + part * a.dy_plane + (size_t)(valid ? r0 + rl : a.dy_zero_row) * a.Cout + cot * 64 + sw;
-      } else {
-        const int kx = TG == 3 ? im - 1 : 0;
-        const int iy = py[h] * a.stride - a.pad + (TG == 3 ? ky : 0), ix = px[h] * a.stride - a.pad + kx;
-        const bool ok = valid && (unsigned)iy < (unsigned)a.IH && (unsigned)ix < (unsigned)a.IW;
-        src = a.in + part * a.in_plane + (size_t)(ok ? (pn[h] * a.IH + iy) * a.IW + ix : a.zero_row) * a.Cin + cit * 64 + sw;
-      }
-      glds16(src, base + im * IMG + part * 2048 + h * 1024);
+    for (int kx = 0; kx < TG; ++kx) {
+      const bool ok = oky && (unsigned)(ix0 + kx) < (unsigned)a.IW;
+      ino[kx] = (size_t)(ok ? irow + kx : a.zero_row) * a.Cin;
     }
-    // the next chunk's pixels
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      px[h] += 16;
-      while (px[h] >= a.OW) { px[h] -= a.OW; py[h] += 1; }
-      while (py[h] >= a.OH) { py[h] -= a.OH; pn[h] += 1; }
-    }
+    r += 16;
+    px += ax; py += ay; irow += d_irow;
+    if (px >= a.OW) { px -= a.OW; py += 1; irow += cx_irow; }
+    if (py >= a.OH) { py -= a.OH; irow += cy_irow; }
+  };
+  // piece ii of NP of that chunk into ring slot `stage`
+  auto piece = [&](int ii, int stage) {
+    const int inst = W + 4 * ii, im = inst / 6, part = (inst % 6) >> 1;      // constants after unrolling
+    const int kx = im >= 1 && im <= TG ? im - 1 : 0;
+    const bf16_t* src = im == 0 ? dyb + part * a.dy_plane + dyo
+                      : im > TG ? dy2b + part * a.dy_plane + dyo
+                                : inb + part * a.in_plane + ino[kx];
+    glds16(src, lds0 + stage * BUF + im * IMG + part * 2048 + H * 1024);
   };
 
-  constexpr int NA = TG + (EXTRA ? 1 : 0);
+  constexpr int NA = TG + (EX ? 1 : 0);
   f32x16 acc[NA];
 #pragma unroll
   for (int j = 0; j < NA; ++j)
@@ -313,55 +441,71 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const SWgradArgs a) {
     for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
 
   // transposed fragment reads: lane l -> channel column (l & 31) of the wave's block, pixels 8 (l >> 5) .. + 7
-  const int cob = wave >> 1, cib = wave & 1;
+  constexpr int cob = W >> 1, cib = W & 1;
   const int kg = lane >> 5, g16 = (lane >> 4) & 1, m = lane & 15, tq = m >> 2, tp = m & 3;
   auto frag = [&](const unsigned char* img, int part, int cb0) -> bf16x8 {
-    const int piece = ((cb0 + 16 * g16) >> 3) + (tp >> 1), inb = (tp & 1) << 3;
+    const int piece = ((cb0 + 16 * g16) >> 3) + (tp >> 1), inb8 = (tp & 1) << 3;
     const int r0 = 8 * kg + tq, r1 = r0 + 4;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + part * 2048 + img_off(r0, piece) + inb));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + part * 2048 + img_off(r1, piece) + inb));
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + part * 2048 + img_off<64>(r0, piece) + inb8));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + part * 2048 + img_off<64>(r1, piece) + inb8));
     typedef short s16x8 __attribute__((ext_vector_type(8)));
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
   };
 
-  if (nchunk > 0) issue(0, 0);
-  for (int q = 0; q < nchunk; ++q) {
-    __syncthreads();
-    if (q + 1 < nchunk) issue(q + 1, (q + 1) & 1);
-    const unsigned char* base = smem + (q & 1) * BUF;
-    bf16x8 fa[3];
+#pragma unroll
+  for (int q = 0; q < D; ++q)
+    if (q < nchunk) {
+      sources();
+#pragma unroll
+      for (int ii = 0; ii < NP; ++ii) piece(ii, q);
+    }
+  int st_read = 0, st_fill = D;                      // ring slots of stage q and of stage q + D
+  // one K step; FILL: stage q + D is requested, two MFMAs between its pieces
+  auto step = [&](int q, auto fill) {
+    constexpr bool FILL = decltype(fill)::value;
+    ring_step<NP, D>(q, nchunk);
+    if constexpr (FILL) sources();
+    const unsigned char* base = smem + st_read * BUF;
+    // every fragment of the step is requested before its first product issues
+    bf16x8 fa[3], fb[TG][3], f2[3];
 #pragma unroll
     for (int p = 0; p < 3; ++p) fa[p] = frag(base, p, 32 * cob);
 #pragma unroll
+    for (int j = 0; j < TG; ++j)
+#pragma unroll
+      for (int p = 0; p < 3; ++p) fb[j][p] = frag(base + (1 + j) * IMG, p, 32 * cib);
+    if constexpr (EX) {
+#pragma unroll
+      for (int p = 0; p < 3; ++p) f2[p] = frag(base + (NIMG - 1) * IMG, p, 32 * cob);
+    }
+    int pk = 0;
+    auto between = [&]() {
+      if constexpr (FILL) {
+        if (pk < NP) piece(pk, st_fill);
+        ++pk;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    if constexpr (FILL) __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
     for (int j = 0; j < TG; ++j) {
-      bf16x8 fb[3];
-#pragma unroll
-      for (int p = 0; p < 3; ++p) fb[p] = frag(base + (1 + j) * IMG, p, 32 * cib);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[2], fb[0], acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[2], acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[1], acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[1], fb[0], acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[1], acc[j], 0, 0, 0);
-      acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[0], fb[0], acc[j], 0, 0, 0);
-      if (EXTRA && j == 1 && extra) {      // the centre tap's input image once more, against the shortcut's dy
-        bf16x8 f2[3];
-#pragma unroll
-        for (int p = 0; p < 3; ++p) f2[p] = frag(base + (NIMG - 1) * IMG, p, 32 * cob);
-        acc[TG] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[2], fb[0], acc[TG], 0, 0, 0);
-        acc[TG] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[0], fb[2], acc[TG], 0, 0, 0);
-        acc[TG] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[1], fb[1], acc[TG], 0, 0, 0);
-        acc[TG] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[1], fb[0], acc[TG], 0, 0, 0);
-        acc[TG] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[0], fb[1], acc[TG], 0, 0, 0);
-        acc[TG] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f2[0], fb[0], acc[TG], 0, 0, 0);
+      six_products(acc[j], fa, fb[j], between);
+      if constexpr (EX) {
+        if (j == 1) six_products(acc[TG], f2, fb[j], between);     // the centre tap's input image once more, against the shortcut's dy
       }
     }
-  }
+    static_assert(NP <= 3 * NA, "a chunk's pieces go between its MFMA pairs");
+    st_read = st_read + 1 == NST ? 0 : st_read + 1;
+    st_fill = st_fill + 1 == NST ? 0 : st_fill + 1;
+  };
+  int q = 0;
+  for (; q + D < nchunk; ++q) step(q, std::true_type());
+  for (; q < nchunk; ++q) step(q, std::false_type());
   const int li = lane & 31, hh = lane >> 5;
   const int taps_total = TG == 3 ? 9 : 1;
 #pragma unroll
   for (int j = 0; j < NA; ++j) {
-    if (j == TG && !extra) continue;
     float* dst = j < TG ? a.slab + ((size_t)split * taps_total + (TG == 3 ? ky * 3 + j : 0)) * a.Cout * a.Cin
                         : a.slab2 + (size_t)split * a.Cout * a.Cin;
 #pragma unroll
@@ -370,6 +514,28 @@ __global__ __launch_bounds__(256) void k_stem_wgrad(const SWgradArgs a) {
       dst[(size_t)co * a.Cin + cit * 64 + 32 * cib + li] = acc[j][i];
     }
   }
+}
+
+template <int TG, bool EX, int D>
+__device__ __forceinline__ void stem_wgrad_waves(const SWgradArgs& a, unsigned char* smem, int wave) {
+  if (wave == 0) stem_wgrad_wave<TG, EX, D, 0>(a, smem);
+  else if (wave == 1) stem_wgrad_wave<TG, EX, D, 1>(a, smem);
+  else if (wave == 2) stem_wgrad_wave<TG, EX, D, 2>(a, smem);
+  else stem_wgrad_wave<TG, EX, D, 3>(a, smem);
+}
+
+template <int TG, bool EXTRA, int D>
+__global__ __launch_bounds__(256) void k_stem_wgrad(const SWgradArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  if constexpr (EXTRA) {
+    const int npair = (a.Cin >> 6) * (a.Cout >> 6);
+    if ((blockIdx.x / npair) % 3 == 1) {               // the ky == 1 workgroups carry the shortcut's accumulator
+      stem_wgrad_waves<TG, true, D>(a, smem, wave);
+      return;
+    }
+  }
+  stem_wgrad_waves<TG, false, D>(a, smem, wave);
 }
 
 // ============================================================================
@@ -828,29 +994,45 @@ __global__ __launch_bounds__(256) void k_stem_reduce(const SReduceArgs a) {
 // ============================================================================
 // launchers
 // ============================================================================
+// NODE_TUNE_STEM_RING=0 (read per call): the one-step, double-buffered schedule of both matrix kernels (A/B runs, tests);
+// the results are the same bits at every depth -- the products enter each accumulator in one order
+static bool stem_ring() { return env_int("NODE_TUNE_STEM_RING", 1) != 0; }
+
 void launch_stem_conv(const SConvArgs& a, hipStream_t s) {
   const int mt = a.cls_tile0[a.nclass];
-  static bool attr[MAX_DEVICES] = {};
-  allow_full_lds(reinterpret_cast<const void*>(k_stem_conv), attr);
-  const size_t lds = 2 * (3 * 128 * 128 + 3 * 64 * 128) + 512;
   const int ntn = (a.Cout / 64) * ((a.mode == 0 && a.w2 != nullptr) ? 2 : 1);
-  hipLaunchKernelGGL(k_stem_conv, dim3(mt * ntn), dim3(256), lds, s, a);
+#define STEM_CONV(KC, D)                                                                  \
+  {                                                                                       \
+    static bool attr[MAX_DEVICES] = {};                                                   \
+    allow_full_lds(reinterpret_cast<const void*>(k_stem_conv<KC, D>), attr);              \
+    const size_t lds = (size_t)(D + 1) * (3 * 128 + 3 * 64) * 2 * KC + 512;               \
+    hipLaunchKernelGGL((k_stem_conv<KC, D>), dim3(mt * ntn), dim3(256), lds, s, a);        \
+  }
+  if (stem_ring()) STEM_CONV(32, STEM_RING_D)
+  else STEM_CONV(64, 1)
+#undef STEM_CONV
 }
 
 void launch_stem_wgrad(const SWgradArgs& a, hipStream_t s) {
   const int taps = a.KH * a.KW;
   const int grid = (a.Cin / 64) * (a.Cout / 64) * (taps == 9 ? 3 : 1) * a.nsplit;
   const int nimg = 1 + (taps == 9 ? 3 : 1) + (a.dy23 ? 1 : 0);
-  const size_t lds = (size_t)2 * nimg * 3 * 16 * 128;
-#define STEM_WG(T, EX)                                                                   \
+#define STEM_WG(T, EX, D)                                                                \
   {                                                                                       \
     static bool attr[MAX_DEVICES] = {};                                                   \
-    allow_full_lds(reinterpret_cast<const void*>(k_stem_wgrad<T, EX>), attr);             \
-    hipLaunchKernelGGL((k_stem_wgrad<T, EX>), dim3(grid), dim3(256), lds, s, a);           \
+    allow_full_lds(reinterpret_cast<const void*>(k_stem_wgrad<T, EX, D>), attr);          \
+    const size_t lds = (size_t)(D + 1) * nimg * 3 * 16 * 128;                             \
+    hipLaunchKernelGGL((k_stem_wgrad<T, EX, D>), dim3(grid), dim3(256), lds, s, a);        \
   }
-  if (taps == 9 && a.dy23) STEM_WG(3, true)
-  else if (taps == 9) STEM_WG(3, false)
-  else STEM_WG(1, false)
+  if (stem_ring()) {
+    if (taps == 9 && a.dy23) STEM_WG(3, true, STEM_RING_D)
+    else if (taps == 9) STEM_WG(3, false, STEM_RING_D)
+    else STEM_WG(1, false, STEM_RING_D)
+  } else {
+    if (taps == 9 && a.dy23) STEM_WG(3, true, 1)
+    else if (taps == 9) STEM_WG(3, false, 1)
+    else STEM_WG(1, false, 1)
+  }
 #undef STEM_WG
 }
 

@@ -109,11 +109,11 @@ def check_statement_sources():
     """Source-level rules for the OTHER hand-written vector-memory asm of the library (advisor finding, round 5): an asm statement
     that loads into registers must carry its own `s_waitcnt vmcnt(0)` (kernels_tiny_solve.hip: the results cannot be used above the
     wait, and the compiler never sees a request in flight) with EARLY-CLOBBER outputs (`=&v`: an output may not share a register with
-    a pointer input of a later request of the same statement); an asm LDS-DMA piece (`global_load_lds_dwordx4`: kernels_w4_wgrad.hip, kernels_w4_diag.hip) has no
+    a pointer input of a later request of the same statement); an asm LDS-DMA piece (`global_load_lds_dwordx4`: kernels_w4_wgrad.hip, kernels_w4_diag.hip, kernels_stem.hip) has no
     register destination at all and must restore M0 in the statement that writes it.  Checked for both the product and the
     diagnostics build: the rules are on the source text."""
     bad = []
-    for fn in ('kernels_tiny_solve.hip', 'kernels_tiny.hip') + W4_FILES:
+    for fn in ('kernels_tiny_solve.hip', 'kernels_tiny.hip', 'kernels_stem.hip') + W4_FILES:
         src = open(os.path.join(CSRC, fn)).read()
         for m in re.finditer(r'asm volatile\((.*?)\);', src, re.S):
             st = m.group(1)
