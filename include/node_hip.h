@@ -478,6 +478,42 @@ size_t node_stem_conv_workspace_bytes(const node_conv_geom* g);
 int node_stem_conv(const node_conv_geom* g, int what, const float* x, const float* w, const float* dy, float* result,
                    void* ws, size_t ws_bytes, void* stream);
 
+/* The residual trunk of the ResNet baseline -- model.py:79 (`features`): `blocks` x ResBlock(channels, channels), stride 1,
+ * identity shortcut (model.py:284-310 with downsample = None).  Per block
+ *     a = relu(norm1(x));  h = conv1(a);  y = conv2(relu(norm2(h))) + x
+ * with norm = nn.GroupNorm(min(32, channels), channels) and both convolutions 3x3 / stride 1 / padding 1 without bias, on
+ * the stem's kernels: gather GEMMs on the bf16 matrix pipe at fp32 accuracy (exact three-way bf16 splits, which keep
+ * fp32's exponent range: no scale anywhere), the residual added in conv2's epilogue, NHWC inside the workspace.
+ * x, out, grad_out, d_x: [n, channels, h, w] NCHW fp32.  taps (NULL: not wanted): [blocks][n, channels, h, w], every
+ * block's output; the last one is `out` bit for bit.
+ *   channels: a power of two in [64, 4096]; blocks >= 1; any n >= 1; h w <= 2400 pixels (the GroupNorm passes hold a
+ *   (sample, channel block) in LDS); tensors under 2^31 elements.  Anything else: NODE_ERR_UNSUPPORTED with a message.
+ * The backward needs the workspace exactly as the forward left it with keep_for_backward = 1 (one workspace per forward
+ * in flight).  It writes (does not accumulate) every parameter gradient and the input gradient d_x (required: the stem
+ * trains behind the trunk).  No floating-point atomics: every sum runs in a fixed order, so results are bit-reproducible
+ * run to run.  The calls never synchronise, allocate device memory or read back.  The workspace-size call returns 0, with
+ * a message behind node_last_error(), for a shape it refuses. */
+typedef struct node_trunk_shape {
+  int32_t n, channels, h, w, blocks;
+  float eps;
+} node_trunk_shape;
+typedef struct node_trunk_block {        /* state_dict keys under `features.<i>.` */
+  const float* n1_w;   /* norm1.weight [channels]                     */
+  const float* n1_b;   /* norm1.bias   [channels]                     */
+  const float* c1_w;   /* conv1.weight [channels, channels, 3, 3]     */
+  const float* n2_w;   /* norm2.weight [channels]                     */
+  const float* n2_b;   /* norm2.bias   [channels]                     */
+  const float* c2_w;   /* conv2.weight [channels, channels, 3, 3]     */
+} node_trunk_block;
+typedef struct node_trunk_block_grads {  /* same order and shapes; device pointers, all required */
+  float* n1_w; float* n1_b; float* c1_w; float* n2_w; float* n2_b; float* c2_w;
+} node_trunk_block_grads;
+size_t node_trunk_workspace_bytes(const node_trunk_shape* shape, int keep_for_backward);
+int node_trunk_fwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* x, float* out, float* taps,
+                   int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_trunk_bwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* grad_out,
+                   const node_trunk_block_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
 /* Retrieval evaluation -- `evaluate.py retrieval` of the reference (evaluate.py:308-361).  For every query i, with scores
  * s_i[j] = q[i] . x[j] and relevance gt_i[j] = (q_labels[i] == x_labels[j]):
  *   ap[i]   = sklearn average_precision_score(gt_i, s_i): descending scores, equal scores form ONE threshold; a row with no

@@ -13,8 +13,9 @@ from .odenet import FCClassifier, ODEDownsample, ODEDownsample2, ODENet, ResBloc
 from . import augment, dp, graphs, optim, retrieval  # noqa: F401
 from .augment import Augmenter, DeviceSplit  # noqa: F401
 from .imgconv import ImageConv2d  # noqa: F401
+from .resnet import ResNet, ResidualTrunk, build_model  # noqa: F401
 from .optim import FusedAdam, FusedSGD  # noqa: F401
 from .head import cross_entropy, linear, linear_cross_entropy  # noqa: F401
 
-__all__ = ['odeint', 'odeint_adjoint', 'ODEBlock', 'ODEfunc', 'ConcatConv2d', 'ODENet', 'StackedODENet',
+__all__ = ['odeint', 'odeint_adjoint', 'ODEBlock', 'ODEfunc', 'ConcatConv2d', 'ODENet', 'StackedODENet', 'ResNet', 'ResidualTrunk',
            'ODEDownsample', 'ODEDownsample2', 'dp']

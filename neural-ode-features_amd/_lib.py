@@ -42,6 +42,7 @@ EXPORTS = [
     'node_retrieval_workspace_bytes', 'node_retrieval_ap', 'node_rank_ap',
     'node_augment_batch',
     'node_imgconv_workspace_bytes', 'node_imgconv_fwd', 'node_imgconv_bwd',
+    'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd',
 ]
 
 
@@ -129,6 +130,18 @@ class NodeStemShape(C.Structure):
 
 class NodeStemParams(C.Structure):          # node_stem_params and node_stem_grads share this layout
     _fields_ = [(k, C.c_void_p) for k in STEM_PARAM_FIELDS]
+
+
+TRUNK_BLOCK_FIELDS = ('n1_w', 'n1_b', 'c1_w', 'n2_w', 'n2_b', 'c2_w')
+
+
+class NodeTrunkShape(C.Structure):
+    _fields_ = [('n', C.c_int32), ('channels', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('blocks', C.c_int32),
+                ('eps', C.c_float)]
+
+
+class NodeTrunkBlock(C.Structure):          # node_trunk_block and node_trunk_block_grads share this layout
+    _fields_ = [(k, C.c_void_p) for k in TRUNK_BLOCK_FIELDS]
 
 
 class NodeConvGeom(C.Structure):
@@ -296,6 +309,12 @@ def load():
     lib.node_imgconv_fwd.argtypes = [P(NodeImgConvShape), vp, vp, vp, vp, vp]
     lib.node_imgconv_bwd.restype = i32
     lib.node_imgconv_bwd.argtypes = [P(NodeImgConvShape), vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.node_trunk_workspace_bytes.restype = sz
+    lib.node_trunk_workspace_bytes.argtypes = [P(NodeTrunkShape), i32]
+    lib.node_trunk_fwd.restype = i32
+    lib.node_trunk_fwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, vp, vp, i32, vp, sz, vp]
+    lib.node_trunk_bwd.restype = i32
+    lib.node_trunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
     ver = lib.node_abi_version()
     if ver != NODE_ABI_VERSION:
         raise RuntimeError('libnode_hip ABI %d != binding ABI %d' % (ver, NODE_ABI_VERSION))

@@ -724,6 +724,9 @@ __global__ __launch_bounds__(256) void k_stem_gn_fwd(const SGnArgs a) {
 
 // backward: da = dL/d relu(GN(h)).  dy = da where the activation is positive; dgamma_c = sum dy xhat, dbeta_c = sum dy;
 // dh = rstd (dy gamma - (s1 + xhat s2) / m) with s1 = sum_group gamma dbeta, s2 = sum_group gamma dgamma
+// SKIP (the residual trunk's block boundary, trunk_api.hip): h also feeds the block's identity shortcut, so its gradient is
+// dh + skip, skip = dL/d(block output); the sum is the next block's output gradient and leaves as fp32 and / or triples.
+template <bool SKIP>
 __global__ __launch_bounds__(256) void k_stem_gn_bwd(const SGnArgs a) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int CB = a.CB, HW = a.HW, C = a.C;
@@ -796,6 +799,11 @@ __global__ __launch_bounds__(256) void k_stem_gn_bwd(const SGnArgs a) {
       v[k] = grstd[g] * (dy * a.gamma[c0 + cc] - (gs1[g] + xh * gs2[g]) * inv_m);
     }
     const size_t o = ((size_t)n * HW + px) * C + c0 + 8 * q;
+    if constexpr (SKIP) {
+      const float4 k0 = *reinterpret_cast<const float4*>(a.skip + o), k1 = *reinterpret_cast<const float4*>(a.skip + o + 4);
+      v[0] += k0.x; v[1] += k0.y; v[2] += k0.z; v[3] += k0.w;
+      v[4] += k1.x; v[5] += k1.y; v[6] += k1.z; v[7] += k1.w;
+    }
     const float4 p0 = make_float4(v[0], v[1], v[2], v[3]), p1 = make_float4(v[4], v[5], v[6], v[7]);
     if (a.dh) {
       *reinterpret_cast<float4*>(a.dh + o) = p0;
@@ -1067,9 +1075,17 @@ void launch_stem_gn_fwd(const SGnArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_stem_gn_fwd, dim3(a.N * (a.C / a.CB)), dim3(256), ((size_t)a.HW * a.CB + 512) * sizeof(float), s, a);
 }
 void launch_stem_gn_bwd(const SGnArgs& a, hipStream_t s) {
-  static bool attr[MAX_DEVICES] = {};
-  allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_bwd), attr);
-  hipLaunchKernelGGL(k_stem_gn_bwd, dim3(a.N * (a.C / a.CB)), dim3(256), ((size_t)2 * a.HW * a.CB + 1024) * sizeof(float), s, a);
+  const dim3 grid(a.N * (a.C / a.CB));
+  const size_t lds = ((size_t)2 * a.HW * a.CB + 1024) * sizeof(float);
+  if (a.skip) {
+    static bool attr[MAX_DEVICES] = {};
+    allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_bwd<true>), attr);
+    hipLaunchKernelGGL(k_stem_gn_bwd<true>, grid, dim3(256), lds, s, a);
+  } else {
+    static bool attr[MAX_DEVICES] = {};
+    allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_bwd<false>), attr);
+    hipLaunchKernelGGL(k_stem_gn_bwd<false>, grid, dim3(256), lds, s, a);
+  }
 }
 
 void launch_stem_prep(const SPrepArgs& a0, hipStream_t s) {

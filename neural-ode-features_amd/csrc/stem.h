@@ -98,6 +98,7 @@ struct SGnArgs {
   bf16_t* dh3;             // nullable triples of the same
   size_t dh_plane;
   float* gpart;            // [N][2][C] per-sample (dgamma, dbeta)
+  const float* skip;       // nullable fp32 NHWC, added to the gradient of h (the residual trunk: h also is the block's shortcut)
   int N, HW, C, cpg, CB;
   float eps;
 };

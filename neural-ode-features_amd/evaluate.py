@@ -18,6 +18,10 @@
              scoring / ranking kernels (retrieval.py) -> retrieval.csv with the reference's columns ap_asym, ap_sym, ap10_asym,
              ap10_sym, t1, plus tol (evaluate.py:308-361)
 
+A run trained with `train --model resnet` (the baseline, resnet.py) takes `features` -- seven "time points": the stem's output and
+the outputs of the six blocks, `t1s = linspace(0, 1, 7)`, `tols = [0]` (evaluate.py:65-67) -- and `retrieval` on them; the modes that
+sweep the ODE block (`nfe`, `tradeoff`, `accuracy`) refuse it.
+
 Runs on a run directory written by `neural_ode_features_amd.train` (or any `{'params', 'model'}` checkpoint with the
 reference's state_dict keys).  Test data: `--data file.pt` (`x_test`, `y_test`) or the synthetic set of that run; a run
 trained with `--augmentation` gets its test transform (augment.py), a run without the key is taken as `none`.
@@ -46,6 +50,7 @@ def load_run(run_dir, which='best'):
         path = os.path.join(run_dir, 'last.pth')
     ckpt = torch.load(path, map_location='cpu', weights_only=False)
     p = types.SimpleNamespace(**ckpt['params'])
+    from .resnet import build_model
     from .train import SHAPES, load_data
     if getattr(p, 'data', None):
         blob = torch.load(p.data, map_location='cpu')
@@ -65,10 +70,19 @@ def load_run(run_dir, which='best'):
         split = nof.DeviceSplit(xte, yte, torch.device('cuda'))
         order = torch.arange(len(split), device=split.device)
         xte = torch.cat([aug.batch(split, order[i:i + 1024], 0, train=False)[0] for i in range(0, len(split), 1024)])
-    model = nof.ODENet(in_ch, out=out, n_filters=p.filters, downsample=p.downsample, method=p.method, tol=p.tol,
-                       adjoint=p.adjoint, dropout=p.dropout, norm=p.norm)
+    model = build_model(p, in_ch, out)           # a ResNet for `params.model == 'resnet'`; no such key: an ODENet
     model.load_state_dict(ckpt['model'])
     return model, p, xte, yte
+
+
+def _is_resnet(p):
+    return getattr(p, 'model', 'odenet') == 'resnet'
+
+
+def _needs_odenet(p, mode):
+    if _is_resnet(p):
+        raise SystemExit('evaluate %s sweeps the ODE block\'s tolerance and integration time: the run is a ResNet, which has no '
+                         'ODE block (its modes: features, retrieval)' % mode)
 
 
 def features(args):
@@ -78,13 +92,18 @@ def features(args):
         xte, yte = xte[:args.limit], yte[:args.limit]
     model = model.to(args.device).eval()
     model.to_features_extractor()
-    model.odeblock.t1 = list(args.t1)
-    if 'ode' in p.downsample:
-        model.downsample.odeblock.t1 = list(args.t1)
+    resnet = _is_resnet(p)
+    if resnet:       # evaluate.py:65-67: seven "time points" (the stem's output and the six blocks'), no tolerance
+        args.t1, args.tol = np.linspace(0, 1, 7).tolist(), [0]
+    else:
+        model.odeblock.t1 = list(args.t1)
+        if 'ode' in p.downsample:
+            model.downsample.odeblock.t1 = list(args.t1)
     feats = []
     with torch.no_grad():
         for tol in args.tol:
-            model.odeblock.tol = tol
+            if not resnet:
+                model.odeblock.tol = tol
             f = [model(xte[i:i + p.batch_size].to(args.device)).cpu().numpy() for i in range(0, xte.shape[0], p.batch_size)]
             feats.append(np.concatenate(f, -2))       # concat along the batch dimension
     out = os.path.join(args.run, 'features.npz')
@@ -97,6 +116,7 @@ def nfe(args):
     """evaluate.py:97-142: per-image function evaluations, batch size 1."""
     import pandas as pd
     model, p, xte, yte = load_run(args.run)
+    _needs_odenet(p, 'nfe')
     if args.limit:
         xte, yte = xte[:args.limit], yte[:args.limit]
     model = model.to(args.device).eval()
@@ -127,6 +147,7 @@ def tradeoff(args):
     import pandas as pd
     import torch.nn.functional as F
     model, p, xte, yte = load_run(args.run)
+    _needs_odenet(p, 'tradeoff')
     if args.limit:
         xte, yte = xte[:args.limit], yte[:args.limit]
     model = model.to(args.device).eval()
@@ -160,6 +181,7 @@ def accuracy(args):
     import pandas as pd
     import torch.nn.functional as F
     model, p, xte, yte = load_run(args.run)
+    _needs_odenet(p, 'accuracy')
     if args.limit:
         xte, yte = xte[:args.limit], yte[:args.limit]
     model = model.to(args.device).eval()

@@ -5,6 +5,9 @@ metrics (loss, acc, NFE-F, NFE-B, test_loss, test_acc, test_nfe), same checkpoin
 schedules (`fixed` / `plateau` / `cosine`, train.py:158-163) -- so a run started by the reference continues here and
 the reverse: the model's state_dict keys and the optimizer's state layout are the reference's.
 
+`--model resnet` trains the baseline of the reference (resnet.py; reproduce.sh: `train.py --model resnet --downsample residual`): no
+solver flag is used, the NFE columns log 0, the run directory is `resnet_<downsample>_f<filters>`; the default stays `odenet`.
+
 What is NOT here (out of the hot path's scope): torchvision datasets and the `expman`
 run-directory bookkeeping.  Data comes from `--data file.pt` (a dict of tensors `x_train, y_train, x_test, y_test`) or, by
 default, a synthetic set of the dataset's shape; the run directory is `--run-dir`.
@@ -29,6 +32,7 @@ import sys
 import torch
 from torch.optim.lr_scheduler import CosineAnnealingLR, LambdaLR, ReduceLROnPlateau
 
+from .resnet import build_model
 from .head import cross_entropy      # F.cross_entropy (train.py:43,93) on the library's kernels; PyTorch's for CPU tensors
 
 AUGMENTATIONS = ('none', 'crop', 'crop+flip+norm', 'crop+jitter+flip+norm')
@@ -208,10 +212,13 @@ def push_log(path, metrics):
         w.writerows(rows)
 
 
-def main(argv=None):
-    parser = argparse.ArgumentParser(description='ODENet training on the HIP backend (flags of the reference train.py:196-225)')
+def build_parser():
+    parser = argparse.ArgumentParser(description='ODENet / ResNet training on the HIP backend (flags of the reference train.py:196-225)')
     stems = ('ode2', 'ode', 'residual', 'convolution', 'minimal', 'one-shot')
     flags = [   # (names, keyword arguments) -- names, defaults and choices are the reference's
+        # train.py:199 of the reference (no default there: reproduce.sh always passes it); `odenet` here, so command lines of
+        # before the flag behave as they did.  `resnet`: the baseline of resnet.py -- the solver flags are not used
+        (('-m', '--model'), dict(type=str, choices=('resnet', 'odenet'), default='odenet')),
         (('--dataset',), dict(type=str, choices=tuple(SHAPES), default='mnist')),
         (('-d', '--downsample'), dict(type=str, choices=stems, default='residual')),
         (('-n', '--norm'), dict(type=str, choices=('group',), default='group')),
@@ -242,15 +249,36 @@ def main(argv=None):
     ]
     for names, kw in flags:
         parser.add_argument(*names, **kw)
-    args = parser.parse_args(argv)
+    return parser
+
+
+def default_run_dir(args):
+    """The run directory of a command line without --run-dir: the solver's settings are part of an ODENet's name only."""
+    if getattr(args, 'model', 'odenet') == 'resnet':
+        name = 'resnet_%s_f%d' % (args.downsample, args.filters)
+    else:
+        name = 'odenet_%s_f%d_%s_tol%g%s' % (args.downsample, args.filters, args.method, args.tol, '_adjoint' if args.adjoint else '')
+    return os.path.join('runs_' + args.dataset, name)
+
+
+def main(argv=None):
+    args = build_parser().parse_args(argv)
+    if args.model == 'resnet':
+        if args.downsample in ('ode', 'ode2'):
+            raise SystemExit('--model resnet takes the stems residual, convolution, minimal and one-shot (model.py:70-77), not %s'
+                             % args.downsample)
+        if args.deferred:
+            # deferred_loop defers the completion read-back of the dopri5 solves (and needs --adjoint --method dopri5 for it);
+            # a ResNet step has no solve, so there is no read-back to defer and no step count that could miss
+            raise SystemExit('--deferred defers the completion of ODE solves: --model resnet has none (its steps never wait '
+                             'for the device); run it without --deferred')
 
     torch.manual_seed(args.seed)
     if not torch.cuda.is_available():
         raise SystemExit('neural_ode_features_amd.train needs a HIP device: the ODE block has no CPU path')
     torch.cuda.manual_seed_all(args.seed)
     args.device = torch.device('cuda')
-    run_dir = args.run_dir or os.path.join('runs_' + args.dataset, 'odenet_%s_f%d_%s_tol%g%s' % (
-        args.downsample, args.filters, args.method, args.tol, '_adjoint' if args.adjoint else ''))
+    run_dir = args.run_dir or default_run_dir(args)
     os.makedirs(run_dir, exist_ok=True)
     log_path, last, best = os.path.join(run_dir, 'log.csv'), os.path.join(run_dir, 'last.pth'), os.path.join(run_dir, 'best.pth')
     if os.path.exists(log_path) and not args.resume:
@@ -267,8 +295,7 @@ def main(argv=None):
                              % (args.augmentation, in_ch))
         aug = nof.Augmenter(args.augmentation, dataset=args.dataset, seed=args.seed)
         train_data, test_data = (nof.DeviceSplit(xtr, ytr, args.device), aug), (nof.DeviceSplit(xte, yte, args.device), aug)
-    model = nof.ODENet(in_ch, out=out, n_filters=args.filters, downsample=args.downsample, method=args.method, tol=args.tol,
-                       adjoint=args.adjoint, dropout=args.dropout, norm=args.norm).to(args.device)
+    model = build_model(args, in_ch, out).to(args.device)       # (shared with evaluate.load_run)
     if args.optim == 'sgd':
         optimizer = nof.FusedSGD(model.parameters(), lr=args.lr, momentum=0.9, weight_decay=args.wd)   # train.py:136
     else:
