@@ -532,6 +532,35 @@ int node_retrieval_ap(int nq, int nd, int d, const float* q, const float* x, con
 int node_rank_ap(int nq, int nd, const float* scores, const int32_t* q_labels, const int32_t* x_labels, int k, double* ap,
                  double* ap_k, void* ws, size_t ws_bytes, void* stream);
 
+/* Finetune evaluation -- `evaluate.py finetune` of the reference (evaluate.py:364-413): the linear SVMs behind
+ * GridSearchCV(LinearSVC(), cv=5), as ONE batch of p problems over a shared x [n, d] (fp32 row-major, device).  Problem j is
+ * the row (fold, cls, c) of `problems` (device): it trains on the rows i with row_fold[i] != fold (fold -1: all rows), with
+ * targets +1 where labels[i] == cls and -1 elsewhere, and minimises, with x~ = [x, 1] (the bias is regularised),
+ *     f(w) = 1/2 |w|^2 + c * sum_i max(0, 1 - y_i w . x~_i)^2                        (LinearSVC's defaults, one-vs-rest)
+ * by a truncated Newton method (conjugate gradients on Hessian-vector products, backtracking line search) whose products
+ * run on the fp32 matrix pipe for all problems at once; per-problem scalars are fp64, the state lives on the device.  A
+ * problem stops when |grad f(w)| <= eps * max(min(#pos, #neg), 1) / #rows * |grad f(0)| (liblinear's rule) and is then
+ * `converged`; after max_iter Newton iterations, or when no step length decreases f any more, it ends with converged = 0.
+ * max_iter = 0 returns zero weights, converged = 0.  weights: [p, d + 1] (device; column d is the intercept); results: [p]
+ * (device).  d <= 280.  Problems are solved in chunks when the workspace would pass 256 MiB.  node_svm_fit reads one word
+ * per Newton iteration from the device and returns after the stream has drained.  Bit-reproducible: no atomics, fixed
+ * summation orders, and a problem's result does not depend on its position in the table (within one chunk).
+ * node_svm_workspace_bytes returns 0 (with a message) for a shape it refuses.
+ *
+ * node_svm_cv_score: group g is the k problems group_problems[g * k ...] (indices into `problems`, one per class in class
+ * order; all of one fold).  For every row held out by that fold it predicts the class of the first maximum of w . x~ over the
+ * group (k = 1: the problem's class iff w . x~ > 0, else neg_class) and counts: correct[g], held[g] (int32, device).  pred,
+ * when not NULL, is int32 [n_groups, n]: the predicted class, -1 for rows that are not held out. */
+typedef struct { int32_t fold; int32_t cls; float c; } node_svm_problem;
+typedef struct { int32_t iterations; int32_t converged; double grad_ratio; } node_svm_result;
+size_t node_svm_workspace_bytes(int n, int d, int p);
+int node_svm_fit(int n, int d, int p, const float* x, const int32_t* labels, const int32_t* row_fold,
+                 const node_svm_problem* problems, double eps, int max_iter, float* weights, node_svm_result* results, void* ws,
+                 size_t ws_bytes, void* stream);
+int node_svm_cv_score(int n, int d, int p, int n_groups, int k, const float* x, const int32_t* labels, const int32_t* row_fold,
+                      const node_svm_problem* problems, const float* weights, const int32_t* group_problems, int neg_class,
+                      int32_t* correct, int32_t* held, int32_t* pred, void* stream);
+
 /* The input pipeline of the training loop -- the transform chains of utils.py:81-196 -- as ONE launch per batch on a split
  * that lives in device memory as uint8:
  *   out[b]        = Normalize(ToTensor(Flip(Jitter(Crop(Pad(data[index[b]]))))))      fp32  [batch, c, h, w]

@@ -40,6 +40,7 @@ EXPORTS = [
     'node_flat_workspace_bytes', 'node_flat_begin', 'node_flat_stage', 'node_flat_scalar', 'node_flat_initial_step',
     'node_flat_finish_step', 'node_flat_status_read',
     'node_retrieval_workspace_bytes', 'node_retrieval_ap', 'node_rank_ap',
+    'node_svm_workspace_bytes', 'node_svm_fit', 'node_svm_cv_score',
     'node_augment_batch',
     'node_imgconv_workspace_bytes', 'node_imgconv_fwd', 'node_imgconv_bwd',
     'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd',
@@ -301,6 +302,12 @@ def load():
     lib.node_retrieval_ap.argtypes = [i32, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, sz, vp]
     lib.node_rank_ap.restype = i32
     lib.node_rank_ap.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp, vp, sz, vp]
+    lib.node_svm_workspace_bytes.restype = sz
+    lib.node_svm_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.node_svm_fit.restype = i32
+    lib.node_svm_fit.argtypes = [i32, i32, i32, vp, vp, vp, vp, C.c_double, i32, vp, vp, vp, sz, vp]
+    lib.node_svm_cv_score.restype = i32
+    lib.node_svm_cv_score.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.node_augment_batch.restype = i32
     lib.node_augment_batch.argtypes = [P(NodeAugment), vp, vp, vp, i32, C.c_uint64, C.c_uint32, vp, vp, vp]
     lib.node_imgconv_workspace_bytes.restype = sz

@@ -534,6 +534,37 @@ void launch_retrieval_scores(const float* q, const float* x, float* scores, int 
 void launch_retrieval_rank(const float* scores, int nq, int nd, const int* qlab, const int* xlab, int k, double* ap, double* ap_k,
                            hipStream_t s);
 
+// finetune evaluation (kernels_svm.hip): P linear SVMs (squared hinge, L2, regularised bias) over one shared X, batched
+// Newton-CG.  SVM_MAX_D: a 64-row slab of X~ and the 64 vectors of a problem tile share the 160 KB of LDS.
+constexpr int SVM_MAX_D = 280;
+struct SvmState {            // per problem, on the device
+  double rr, gnorm, gnorm0, thresh, cg_tol2, ratio;
+  int n_train, n_pos, iters, done, converged, cg_done, cg_iters, pad;
+};
+struct SvmPlan {
+  int n, d, p;
+  int slabs, slabs_per_group, groups;      // 64-row slabs of X; a workgroup owns slabs_per_group of them; partials per problem
+  int ls_rows, ls_groups, ls_nc;           // line search: rows per block, blocks, step lengths
+};
+SvmPlan svm_plan(int n, int d, int p);
+void launch_svm_init(const SvmPlan& pl, const int* labels, const int* row_fold, const node_svm_problem* prob, SvmState* st, float* w,
+                     hipStream_t s);
+// mode 0: v = w, writes Z, part = X~^T (A o (z - y));  1: v = d, part = X~^T (A o X~ d);  2: v = s, writes XS = X~ s only
+void launch_svm_product(const SvmPlan& pl, int mode, const float* x, const int* labels, const int* row_fold,
+                        const node_svm_problem* prob, const SvmState* st, const float* v, float* zbuf, float* xsbuf, float* part,
+                        hipStream_t s);
+void launch_svm_newton_begin(const SvmPlan& pl, const float* part, const float* w, float* g, float* sv, float* rv, float* dv,
+                             SvmState* st, const node_svm_problem* prob, int last, double eps, hipStream_t s);
+void launch_svm_cg_step(const SvmPlan& pl, const float* part, float* sv, float* rv, float* dv, SvmState* st,
+                        const node_svm_problem* prob, int cg_max, hipStream_t s);
+void launch_svm_line_search(const SvmPlan& pl, const float* zbuf, const float* xsbuf, const int* labels, const int* row_fold,
+                            const node_svm_problem* prob, SvmState* st, double* lspart, float* w, const float* sv, const float* g,
+                            hipStream_t s);
+void launch_svm_status(const SvmPlan& pl, const SvmState* st, node_svm_result* res, int* flag, hipStream_t s);
+void launch_svm_cv_score(int n, int d, int n_groups, int k, const float* x, const int* labels, const int* row_fold,
+                         const node_svm_problem* prob, const float* w, const int* group_problems, int neg_class, int* correct,
+                         int* held, int* pred, hipStream_t s);
+
 // input pipeline (kernels_augment.hip): gather + crop / jitter / flip / normalise of a batch of dataset indices, one launch.
 // The stage bits are the NODE_AUG_* of include/node_hip.h (augment_api.hip asserts that they agree).
 constexpr uint32_t AUG_CROP = 1, AUG_JITTER = 2, AUG_FLIP = 4, AUG_NORM = 8;

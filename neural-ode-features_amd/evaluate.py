@@ -17,10 +17,14 @@
              the test set (database at the last slice 'asym' and at the query's own slice 'sym'), AP and AP@10 on the HIP
              scoring / ranking kernels (retrieval.py) -> retrieval.csv with the reference's columns ap_asym, ap_sym, ap10_asym,
              ap10_sym, t1, plus tol (evaluate.py:308-361)
+  finetune   reads features.npz too: per tolerance slice, per t1 slice (or, with -a / --aggregate, their mean over t1 as one
+             slice t1 = -1), `GridSearchCV(LinearSVC(), C = logspace(-2, 2, 5), cv=5)` as one batch of SVM problems on the HIP
+             solver (finetune.py) -> finetune.csv with the reference's columns block, t1, cv_accuracy, plus tol, and the refit
+             at the best C per slice in svms/svm_b{block}_t{t1}.npz (evaluate.py:364-413)
 
 A run trained with `train --model resnet` (the baseline, resnet.py) takes `features` -- seven "time points": the stem's output and
-the outputs of the six blocks, `t1s = linspace(0, 1, 7)`, `tols = [0]` (evaluate.py:65-67) -- and `retrieval` on them; the modes that
-sweep the ODE block (`nfe`, `tradeoff`, `accuracy`) refuse it.
+the outputs of the six blocks, `t1s = linspace(0, 1, 7)`, `tols = [0]` (evaluate.py:65-67) -- and `retrieval` and `finetune` on them; the
+modes that sweep the ODE block (`nfe`, `tradeoff`, `accuracy`) refuse it.
 
 Runs on a run directory written by `neural_ode_features_amd.train` (or any `{'params', 'model'}` checkpoint with the
 reference's state_dict keys).  Test data: `--data file.pt` (`x_test`, `y_test`) or the synthetic set of that run; a run
@@ -29,6 +33,7 @@ trained with `--augmentation` gets its test transform (augment.py), a run withou
     python -m neural_ode_features_amd.evaluate features runs_cifar10/odenet --t1 0 0.5 1 --tol 1e-3 1e-1
     python -m neural_ode_features_amd.evaluate nfe runs_cifar10/odenet --limit 100
     python -m neural_ode_features_amd.evaluate retrieval runs_cifar10/odenet
+    python -m neural_ode_features_amd.evaluate finetune runs_cifar10/odenet --aggregate
 """
 from __future__ import annotations
 
@@ -82,7 +87,7 @@ def _is_resnet(p):
 def _needs_odenet(p, mode):
     if _is_resnet(p):
         raise SystemExit('evaluate %s sweeps the ODE block\'s tolerance and integration time: the run is a ResNet, which has no '
-                         'ODE block (its modes: features, retrieval)' % mode)
+                         'ODE block (its modes: features, retrieval, finetune)' % mode)
 
 
 def features(args):
@@ -257,15 +262,80 @@ def retrieval(args, k=10):
     return out
 
 
+def _run_params(run_dir, which='best'):
+    """The `params` of the run's checkpoint alone (no model, no data)."""
+    path = os.path.join(run_dir, which + '.pth')
+    if not os.path.exists(path):
+        path = os.path.join(run_dir, 'last.pth')
+    if not os.path.exists(path):
+        raise SystemExit('no checkpoint found in %s (best.pth / last.pth)' % run_dir)
+    return types.SimpleNamespace(**torch.load(path, map_location='cpu', weights_only=False)['params'])
+
+
+def _svc_search(feats, y_true):
+    """One slice's grid search on the device: `finetune.linear_svc_cv` on features [N, D] (numpy) and labels."""
+    from .finetune import linear_svc_cv
+    if not torch.cuda.is_available():
+        raise SystemExit('neural_ode_features_amd.evaluate needs a HIP device: the SVM solver has no CPU path')
+    dev = torch.device('cuda')
+    x = torch.from_numpy(np.ascontiguousarray(feats, dtype=np.float32)).to(dev)
+    return linear_svc_cv(x, torch.from_numpy(np.asarray(y_true).astype(np.int64)).to(dev))
+
+
+def finetune(args):
+    """evaluate.py:364-413: the 5-fold cross-validated accuracy of a linear SVM (C searched over logspace(-2, 2, 5)) on the
+    features of every time slice, as one batch of problems per slice on the HIP solver of `finetune.linear_svc_cv` instead of
+    sklearn's GridSearchCV on the host.
+
+    The reference's `features()` writes `[tols, T, N, D]` while its `finetune()` indexes `[T, N, D]`, so the reference loop runs
+    here once per tolerance slice.  Kept as written: `--aggregate` replaces the slices by their mean over T with `t1 = -1`;
+    for `downsample == 'ode'` runs the slices are those of the ODE stem then those of the ODE block, `block = [0] * T + [1] * T`
+    with `t1s` doubled; slices, `t1s` and `block` are zipped.  -> finetune.csv with the reference's columns block, t1,
+    cv_accuracy, plus tol: one row per (tol, slice); the refit at the best C (the reference pickles the estimator) as `coef
+    [K, D]`, `intercept [K]`, `C` and `classes` in svms/svm_b{block}_t{t1}.npz, with `_tol{tol}` before the suffix when the
+    features hold more than one tolerance."""
+    import pandas as pd
+    path = os.path.join(args.run, 'features.npz')
+    if not os.path.exists(path):
+        raise SystemExit('no pre-extracted features found: %s (run the `features` mode first)' % path)
+    p = _run_params(args.run)
+    with np.load(path) as f:
+        feats, y_true, t1s, tols = f['features'], f['y_true'], f['t1s'], f['tols']
+    svm_dir = os.path.join(args.run, 'svms')
+    os.makedirs(svm_dir, exist_ok=True)
+    rows = []
+    for ti, tol in enumerate(tols):
+        fs, ts = feats[ti], t1s                                                          # [T, N, D]
+        if getattr(args, 'aggregate', False):
+            fs, ts = fs.mean(0, keepdims=True), np.array([-1])
+        block = np.zeros(len(ts), dtype=int)
+        if getattr(p, 'downsample', None) == 'ode':
+            block, ts = np.concatenate((block, block + 1)), np.concatenate((ts, ts))
+        for t1, b, fi in zip(ts, block, fs):
+            search = _svc_search(fi, y_true)
+            rows.append({'block': int(b), 't1': t1, 'cv_accuracy': search.best_score, 'tol': tol})
+            name = 'svm_b%d_t%g%s.npz' % (b, t1, '_tol%g' % tol if len(tols) > 1 else '')
+            np.savez(os.path.join(svm_dir, name), coef=search.coef, intercept=search.intercept, C=search.best_C,
+                     classes=search.classes)
+    out = os.path.join(args.run, 'finetune.csv')
+    df = pd.DataFrame(rows, columns=['block', 't1', 'cv_accuracy', 'tol'])
+    df.to_csv(out, index=False)
+    print(df)
+    return out
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(description='features / nfe / tradeoff / accuracy / retrieval evaluations of the reference on the HIP '
+    ap = argparse.ArgumentParser(description='features / nfe / tradeoff / accuracy / retrieval / finetune evaluations of the reference on the HIP '
                                              'backend')
-    ap.add_argument('mode', choices=('features', 'nfe', 'tradeoff', 'accuracy', 'retrieval'))
+    ap.add_argument('mode', choices=('features', 'nfe', 'tradeoff', 'accuracy', 'retrieval', 'finetune'))
     ap.add_argument('run')
     ap.add_argument('--t1', type=float, nargs='+', default=np.arange(0, 1.05, .05).tolist())      # evaluate.py:424
     ap.add_argument('--tol', type=float, nargs='+', default=[1e-3, 1e-2, 1e-1, 1e0, 1e1, 1e2])      # evaluate.py:423
     ap.add_argument('--limit', type=int, default=0, help='only the first N test images')
+    ap.add_argument('-a', '--aggregate', action='store_true', help='finetune: one slice, the mean of the features over t1')
     args = ap.parse_args(argv)
+    if args.mode == 'finetune':          # reads files only; the solver asks for the device when the first slice reaches it
+        return finetune(args)
     if not torch.cuda.is_available():
         raise SystemExit('neural_ode_features_amd.evaluate needs a HIP device: the ODE block has no CPU path')
     args.device = torch.device('cuda')
