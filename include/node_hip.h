@@ -466,6 +466,20 @@ int node_stem_fwd(const node_stem_shape* shape, const node_stem_params* params, 
                   void* ws, size_t ws_bytes, void* stream);
 int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* params, const float* x, const float* grad_out,
                   const node_stem_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* node_stem_bwd plus the gradient of the image, d_x [n, in_ch, h, w] NCHW fp32 (required; written, not accumulated): behind
+ * the data-gradient chain that ends at the first layer's output, one more kernel -- the transposed first layer
+ *     d_x[n][ci][y][x] = sum_co sum_ky,kx dh0[n][y - ky][x - kx][co] * w0[co][ci][ky][kx]
+ * in fp32 without atomics (the same bits on every run).  grads may be NULL (saliency maps, adversarial attacks: frozen
+ * parameters): then only the data-gradient chain runs -- the dgrad convolutions, the GroupNorm backward passes, the
+ * F(4x4,3x3) dgrad where the stem takes that pipeline -- and no weight-gradient or slab-reduction launch.  With grads given,
+ * the parameter gradients are node_stem_bwd's bit for bit.  Same workspace contract as node_stem_bwd. */
+int node_stem_bwd_dx(const node_stem_shape* shape, const node_stem_params* params, const float* x, const float* grad_out,
+                     const node_stem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+/* Diagnostics (tests, tools): the transposed first layer alone on NCHW tensors.  w0: [64, in_ch, 3, 3];
+ * dy: [n, 64, h - 2, w - 2]; d_x: [n, in_ch, h, w]; shape->filters and shape->eps are ignored; any h, w >= 3. */
+size_t node_stem_conv0_dgrad_workspace_bytes(const node_stem_shape* shape);
+int node_stem_conv0_dgrad(const node_stem_shape* shape, const float* w0, const float* dy, float* d_x,
+                          void* ws, size_t ws_bytes, void* stream);
 
 /* Diagnostics (tests): ONE convolution of the stem's kernel family on NCHW fp32 tensors, through the same layout /
  * split / MFMA kernels node_stem_fwd and node_stem_bwd use.  what: 0 forward y = conv2d(x, w, stride, pad);
@@ -622,6 +636,48 @@ int node_imgconv_bwd(const node_imgconv_shape* shape, const float* x, const floa
  * recorded events and fills `out`. */
 int node_profile_begin(void);
 int node_profile_end(node_profile* out);
+
+/* The basic-iterative (BIM / PGD) attack's per-iteration arithmetic -- adversarial/attack.py:72 (foolbox 2.x
+ * LinfinityBasicIterativeAttack / L2BasicIterativeAttack with binary_search=False, no random start, untargeted,
+ * Misclassification).  Images are [n, c, h, w] fp32 in pixel space [lo, hi]; s = hi - lo.  Two launches per iteration for the
+ * whole batch, one workgroup per sample; neither synchronises, allocates or reads back.
+ *
+ * node_attack_step: for every sample with active[i] != 0, with g the gradient of the loss with respect to the NORMALISED
+ * model input (x - mean) / std (the kernel divides it by std):
+ *     L-infinity: x += stepsize * sign(g) * s;                      p = clip(x - x0, -epsilon s, epsilon s)
+ *     L2:         x += stepsize * g / max(1e-12, rms(g)) * s;       p = (x - x0) * min(1, epsilon s / max(1e-12, rms(x - x0)))
+ *     x = clip(x0 + p, lo, hi);   x_norm = (x - mean) / std         (rms: root MEAN square over the sample)
+ * x is updated in place.  An inactive sample keeps x and x_norm bit for bit.  Any c h w.
+ *
+ * node_attack_judge: predicted class = arg-max of logits [n, classes] (first index on ties).  initial != 0: writes
+ * original_class; a sample whose prediction differs from its label (a natural error) gets distance 0, adversarial_class =
+ * the prediction, found_iteration 0 and active = 0.  Otherwise, for an active sample whose prediction differs from its
+ * label: distance = mean((x - x0)^2) / s^2 (L2) or max |x - x0| / s (L-infinity); with return_early the record
+ * (adversarial_class, found_iteration = iteration, distance, and best_x if given) is written and active cleared; without, the sample
+ * stays active and the record and best_x (required) are replaced only by a strictly smaller distance.  The caller
+ * initialises active = 1, adversarial_class = -1, found_iteration = -1, distance = +inf. */
+#define NODE_ATTACK_LINF 0
+#define NODE_ATTACK_L2 2
+typedef struct node_attack {
+  int32_t n, c, h, w;
+  int32_t norm;              /* NODE_ATTACK_LINF or NODE_ATTACK_L2 */
+  int32_t return_early;
+  double stepsize, epsilon, lo, hi;
+  const float* mean;         /* device [c], or NULL with std: no preprocessing */
+  const float* std;
+} node_attack;
+typedef struct node_attack_record {    /* device pointers, one entry per sample */
+  int32_t* active;
+  int32_t* original_class;
+  int32_t* adversarial_class;
+  int32_t* found_iteration;
+  float* distance;
+  float* best_x;             /* [n, c, h, w]; nullable with return_early */
+} node_attack_record;
+int node_attack_step(const node_attack* attack, float* x, const float* x0, const float* g, const int32_t* active,
+                     float* x_norm, void* stream);
+int node_attack_judge(const node_attack* attack, int classes, const float* logits, const int64_t* labels, const float* x,
+                      const float* x0, int initial, int iteration, const node_attack_record* record, void* stream);
 
 #ifdef __cplusplus
 }

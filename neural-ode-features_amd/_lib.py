@@ -36,6 +36,7 @@ EXPORTS = [
     'node_sgd_step', 'node_adam_step', 'node_profile_begin', 'node_profile_end',
     'node_conv3x3_w4_workspace_bytes', 'node_conv3x3_w4', 'node_w4_split3', 'node_w4_pair_stats',
     'node_stem_workspace_bytes', 'node_stem_fwd', 'node_stem_bwd', 'node_stem_conv_workspace_bytes', 'node_stem_conv',
+    'node_stem_bwd_dx', 'node_stem_conv0_dgrad_workspace_bytes', 'node_stem_conv0_dgrad', 'node_attack_step', 'node_attack_judge',
     'node_head_loss_scratch_bytes', 'node_head_loss_fwd', 'node_head_loss_bwd',
     'node_flat_workspace_bytes', 'node_flat_begin', 'node_flat_stage', 'node_flat_scalar', 'node_flat_initial_step',
     'node_flat_finish_step', 'node_flat_status_read',
@@ -190,6 +191,19 @@ class NodeImgConvShape(C.Structure):
     _fields_ = [('n', C.c_int32), ('in_ch', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('filters', C.c_int32)]
 
 
+ATTACK_LINF, ATTACK_L2 = 0, 2
+
+
+class NodeAttack(C.Structure):
+    _fields_ = [('n', C.c_int32), ('c', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('norm', C.c_int32),
+                ('return_early', C.c_int32), ('stepsize', C.c_double), ('epsilon', C.c_double), ('lo', C.c_double),
+                ('hi', C.c_double), ('mean', C.c_void_p), ('std', C.c_void_p)]
+
+
+class NodeAttackRecord(C.Structure):
+    _fields_ = [(k, C.c_void_p) for k in ('active', 'original_class', 'adversarial_class', 'found_iteration', 'distance', 'best_x')]
+
+
 class NodeHipError(RuntimeError):
     def __init__(self, code, message):
         self.code = code
@@ -276,6 +290,16 @@ def load():
     lib.node_stem_conv_workspace_bytes.argtypes = [P(NodeConvGeom)]
     lib.node_stem_conv.restype = i32
     lib.node_stem_conv.argtypes = [P(NodeConvGeom), i32, vp, vp, vp, vp, vp, sz, vp]
+    lib.node_stem_bwd_dx.restype = i32
+    lib.node_stem_bwd_dx.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, P(NodeStemParams), vp, vp, sz, vp]
+    lib.node_stem_conv0_dgrad_workspace_bytes.restype = sz
+    lib.node_stem_conv0_dgrad_workspace_bytes.argtypes = [P(NodeStemShape)]
+    lib.node_stem_conv0_dgrad.restype = i32
+    lib.node_stem_conv0_dgrad.argtypes = [P(NodeStemShape), vp, vp, vp, vp, sz, vp]
+    lib.node_attack_step.restype = i32
+    lib.node_attack_step.argtypes = [P(NodeAttack), vp, vp, vp, vp, vp, vp]
+    lib.node_attack_judge.restype = i32
+    lib.node_attack_judge.argtypes = [P(NodeAttack), i32, vp, vp, vp, vp, i32, i32, P(NodeAttackRecord), vp]
     lib.node_head_loss_scratch_bytes.restype = sz
     lib.node_head_loss_scratch_bytes.argtypes = [i32]
     lib.node_head_loss_fwd.restype = i32

@@ -639,6 +639,66 @@ __global__ __launch_bounds__(256) void k_stem_conv0_wgrad(const float* __restric
   }
 }
 
+// d_x[n][ci][y][x] = sum_co sum_ky,kx dh0[n][y - ky][x - kx][co] * w0[co][ci][ky][kx]: the transposed first layer, 64 -> Cin <= 3
+// channels.  One workgroup per (sample, DG_TH x DG_TW tile of IMAGE pixels):
+//   1. P[pixel][k] = sum_co dh0[pixel][co] * w0[co][k] for the (DG_TH + 2) x (DG_TW + 2) pixels of dh0 that reach the tile, on the
+//      fp32 matrix instruction (32 pixels x 28 columns per wave tile, K = 64 channels: lane half hh owns channels 32 hh .. 32 hh + 31 of
+//      its pixel, eight float4 loads of one NHWC row), the tile in LDS; a pixel outside dh0 is a zero row, so
+//   2. every image pixel gathers nine entries of P in one fixed order (border pixels: the taps that fall outside are those zero rows).
+// fp32 throughout, no atomics: the same bits on every run.
+constexpr int DG_TH = 8, DG_TW = 32, DG_PH = DG_TH + 2, DG_PW = DG_TW + 2, DG_NP = DG_PH * DG_PW, DG_NT = (DG_NP + 31) / 32, DG_PS = 29;
+__global__ __launch_bounds__(256) void k_stem_conv0_dgrad(const float* __restrict__ dh0, const float* __restrict__ w0,
+                                                          float* __restrict__ dx, int Cin, int H, int W, int tiles_x, int tiles_y) {
+  __shared__ float P[DG_NT * 32 * DG_PS];
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, li = lane & 31, hh = lane >> 5;
+  const int OH = H - 2, OW = W - 2, K = 9 * Cin;
+  const int n = blockIdx.x / (tiles_x * tiles_y), rem = blockIdx.x - n * tiles_x * tiles_y, ty = rem / tiles_x, tx = rem - ty * tiles_x;
+  const int y0 = ty * DG_TH, x0 = tx * DG_TW;
+  float b[32];                     // w0[32 hh + s][li]: the filter as [64][K], column li (columns >= K are zero)
+#pragma unroll
+  for (int s = 0; s < 32; ++s) b[s] = li < K ? w0[(32 * hh + s) * K + li] : 0.f;
+  for (int tile = wave; tile < DG_NT; tile += 4) {
+    const int pix = tile * 32 + li, py = pix / DG_PW, px = pix - py * DG_PW;
+    const int oy = y0 - 2 + py, ox = x0 - 2 + px;
+    const bool valid = pix < DG_NP && oy >= 0 && oy < OH && ox >= 0 && ox < OW;
+    float4 av[8];
+    if (valid) {
+      const float4* src = reinterpret_cast<const float4*>(dh0 + ((size_t)(n * OH + oy) * OW + ox) * 64 + 32 * hh);
+#pragma unroll
+      for (int q = 0; q < 8; ++q) av[q] = src[q];
+    } else {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) av[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    f32x16 acc;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].x, b[4 * q], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].y, b[4 * q + 1], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].z, b[4 * q + 2], acc, 0, 0, 0);
+      acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q].w, b[4 * q + 3], acc, 0, 0, 0);
+    }
+    if (li < 28) {
+#pragma unroll
+      for (int i = 0; i < 16; ++i) P[(tile * 32 + 8 * (i >> 2) + 4 * hh + (i & 3)) * DG_PS + li] = acc[i];
+    }
+  }
+  __syncthreads();
+  for (int idx = t; idx < Cin * DG_TH * DG_TW; idx += 256) {
+    const int xx = idx % DG_TW, yy = (idx / DG_TW) % DG_TH, ci = idx / (DG_TW * DG_TH);
+    const int y = y0 + yy, x = x0 + xx;
+    if (y >= H || x >= W) continue;
+    float s = 0.f;
+#pragma unroll
+    for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) s += P[((yy + 2 - ky) * DG_PW + xx + 2 - kx) * DG_PS + ci * 9 + ky * 3 + kx];
+    dx[((size_t)(n * Cin + ci) * H + y) * W + x] = s;
+  }
+}
+
 // ============================================================================
 // GroupNorm + ReLU.  One workgroup per (sample, CB channels); the block [HW][CB] lives in LDS.
 //   thread -> channel t % CB (fixed), pixels t / CB, t / CB + 256 / CB, ...; group sums through LDS
@@ -1051,6 +1111,10 @@ void launch_stem_conv0_fwd(const float* x, const float* w0t, const float* bias, 
 void launch_stem_conv0_wgrad(const float* x, const float* dh0, float* slab, int N, int Cin, int H, int W, int nsplit, int rows_per_split,
                              hipStream_t s) {
   hipLaunchKernelGGL(k_stem_conv0_wgrad, dim3(nsplit), dim3(256), 0, s, x, dh0, slab, N, Cin, H, W, rows_per_split);
+}
+void launch_stem_conv0_dgrad(const float* dh0, const float* w0, float* dx, int N, int Cin, int H, int W, hipStream_t s) {
+  const int tx = (W + DG_TW - 1) / DG_TW, ty = (H + DG_TH - 1) / DG_TH;
+  hipLaunchKernelGGL(k_stem_conv0_dgrad, dim3((unsigned)(N * tx * ty)), dim3(256), 0, s, dh0, w0, dx, Cin, H, W, tx, ty);
 }
 
 // channels per workgroup of the GroupNorm passes: a power of two in [max(8, cpg), 128] whose [HW][CB] block fits the LDS

@@ -81,6 +81,9 @@ void launch_stem_conv0_fwd(const float* x, const float* w0t /*[28][64]*/, const 
 // slab [nsplit][64][32]: column k < 9 Cin = dW0[co][k], column 9 Cin = the bias gradient
 void launch_stem_conv0_wgrad(const float* x, const float* dh0, float* slab, int N, int Cin, int H, int W, int nsplit,
                              int rows_per_split, hipStream_t s);
+// the transposed first layer: d_x [N][Cin][H][W] (NCHW, every element written) from dh0 [N (H - 2) (W - 2)][64] (NHWC) and the filter
+// as PyTorch holds it, w0 [64][Cin][3][3]
+void launch_stem_conv0_dgrad(const float* dh0, const float* w0, float* dx, int N, int Cin, int H, int W, hipStream_t s);
 
 // ----------------------------------------------------------------------------
 // GroupNorm + ReLU passes (one workgroup per (sample, block of CB channels), the block held in LDS)

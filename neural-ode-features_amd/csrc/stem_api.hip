@@ -259,16 +259,21 @@ int node_stem_fwd(const node_stem_shape* shape, const node_stem_params* prm, con
   return launch_ok("node_stem_fwd");
 }
 
-int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, const float* grad_out,
-                  const node_stem_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+// node_stem_bwd (gr given, d_x NULL) and node_stem_bwd_dx (d_x given; gr NULL: the data-gradient chain alone -- no weight-gradient,
+// no slab-reduction launch)
+int stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, const float* grad_out,
+             const node_stem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream, const char* who) {
   w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)
   int rc = check_stem_shape(shape);
   if (rc != NODE_OK) return rc;
-  if (!prm || !x || !grad_out || !gr || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if (!prm || !x || !grad_out || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
   const float* const* pp = reinterpret_cast<const float* const*>(prm);
   float* const* gp = reinterpret_cast<float* const*>(gr);
   for (int i = 0; i < 16; ++i)
-    if (!pp[i] || !gp[i]) return fail(NODE_ERR_NULL, "stem parameter / gradient %d is NULL", i);
+    if (!pp[i] || (gr && !gp[i])) return fail(NODE_ERR_NULL, "stem parameter / gradient %d is NULL", i);
   if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
   StemPlan p = make_stem_plan(shape, ws);
   if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
@@ -295,17 +300,21 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, con
     if ((rc = launch_ok("w4s_pass")) != NODE_OK) return rc;
     launch_stem_split(p.dh3n, p.dh3t.p, p.dh3t.plane, (size_t)p.R2 * F, st);
     if ((rc = launch_ok("stem_split")) != NODE_OK) return rc;
-    W4WgradArgs wa;
-    memset(&wa, 0, sizeof(wa));
-    wa.V1 = p.Va; wa.Z1 = p.Z4; wa.dU = p.dU4; wa.N = N; wa.C = F;
-    launch_w4_wgrad(wa, st);
-    if ((rc = launch_ok("w4_wgrad")) != NODE_OK) return rc;
-    launch_w4_du_to_dw(p.dU4, gr->b2_c2_w, F, st);
-    if ((rc = launch_ok("w4_du_to_dw")) != NODE_OK) return rc;
+    if (gr) {
+      W4WgradArgs wa;
+      memset(&wa, 0, sizeof(wa));
+      wa.V1 = p.Va; wa.Z1 = p.Z4; wa.dU = p.dU4; wa.N = N; wa.C = F;
+      launch_w4_wgrad(wa, st);
+      if ((rc = launch_ok("w4_wgrad")) != NODE_OK) return rc;
+      launch_w4_du_to_dw(p.dU4, gr->b2_c2_w, F, st);
+      if ((rc = launch_ok("w4_du_to_dw")) != NODE_OK) return rc;
+    }
   } else {
   // block 2, conv2 (3x3, F -> F) : weight gradient, data gradient -> da3
-    launch_stem_wgrad(wgrad_args(p.g3, nullptr, p.a3, p.w4, N, p.H2, p.W2, p.H2, p.W2, F, F, 3, 1, 1), st);
-    if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+    if (gr) {
+      launch_stem_wgrad(wgrad_args(p.g3, nullptr, p.a3, p.w4, N, p.H2, p.W2, p.H2, p.W2, F, F, 3, 1, 1), st);
+      if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+    }
     launch_stem_conv(conv_dgrad_args(p.g3, p.c4, p.da3, N, p.H2, p.W2, p.H2, p.W2, 3, 1, 1), st);
     if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
     {
@@ -316,8 +325,10 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, con
     }
   }
   // block 2, conv1 (3x3 / 2, 64 -> F) + shortcut (1x1 / 2, 64 -> F): both read a2
-  launch_stem_wgrad(wgrad_args(p.dh3t, &p.g3, p.a2, p.w3, N, p.H1, p.W1, p.H2, p.W2, 64, F, 3, 2, 1), st);
-  if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  if (gr) {
+    launch_stem_wgrad(wgrad_args(p.dh3t, &p.g3, p.a2, p.w3, N, p.H1, p.W1, p.H2, p.W2, 64, F, 3, 2, 1), st);
+    if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  }
   {   // data gradient of conv1 (3x3 / 2) + the shortcut's (1x1 / 2: one more K segment of the (even, even) pixels)
     SConvArgs c = conv_dgrad_args(p.dh3t, p.c3, p.da2, N, p.H2, p.W2, p.H1, p.W1, 3, 2, 1);
     c.in2 = p.g3.p; c.w2 = p.d2.wd; c.w2_plane = p.d2.plane;
@@ -331,8 +342,10 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, con
     if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
   }
   // block 1, conv2 (3x3, 64 -> 64): dx1 is the gradient of its output AND of the shortcut s1
-  launch_stem_wgrad(wgrad_args(p.dx1t, nullptr, p.a1, p.w2, N, p.H1, p.W1, p.H1, p.W1, 64, 64, 3, 1, 1), st);
-  if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  if (gr) {
+    launch_stem_wgrad(wgrad_args(p.dx1t, nullptr, p.a1, p.w2, N, p.H1, p.W1, p.H1, p.W1, 64, 64, 3, 1, 1), st);
+    if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  }
   launch_stem_conv(conv_dgrad_args(p.dx1t, p.c2, p.da1, N, p.H1, p.W1, p.H1, p.W1, 3, 1, 1), st);
   if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
   {
@@ -342,8 +355,10 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, con
     if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
   }
   // block 1, conv1 (3x3 / 2) + shortcut (1x1 / 2): both read a0
-  launch_stem_wgrad(wgrad_args(p.dh1t, &p.dx1t, p.a0, p.w1, N, p.H0, p.W0, p.H1, p.W1, 64, 64, 3, 2, 1), st);
-  if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  if (gr) {
+    launch_stem_wgrad(wgrad_args(p.dh1t, &p.dx1t, p.a0, p.w1, N, p.H0, p.W0, p.H1, p.W1, 64, 64, 3, 2, 1), st);
+    if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  }
   {
     SConvArgs c = conv_dgrad_args(p.dh1t, p.c1, p.da0, N, p.H1, p.W1, p.H0, p.W0, 3, 2, 1);
     c.in2 = p.dx1t.p; c.w2 = p.d1.wd; c.w2_plane = p.d1.plane;
@@ -356,6 +371,11 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, con
     launch_stem_gn_bwd(g, st);
     if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
   }
+  if (d_x) {   // the transposed first layer: dh0 -> the image
+    launch_stem_conv0_dgrad(p.dh0, prm->conv0_w, d_x, N, p.Cin0, p.H, p.W, st);
+    if ((rc = launch_ok("stem_conv0_dgrad")) != NODE_OK) return rc;
+  }
+  if (!gr) return launch_ok(who);
   launch_stem_conv0_wgrad(x, p.dh0, p.w0.slab, N, p.Cin0, p.H, p.W, p.w0.nsplit, p.w0.rps, st);
   if ((rc = launch_ok("stem_conv0_wgrad")) != NODE_OK) return rc;
 
@@ -376,7 +396,25 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, con
   ra.njobs = nj;
   launch_stem_reduce(ra, st);
   if ((rc = launch_ok("stem_reduce")) != NODE_OK) return rc;
-  return launch_ok("node_stem_bwd");
+  return launch_ok(who);
+}
+}  // namespace
+
+extern "C" {
+
+int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, const float* grad_out,
+                  const node_stem_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+  if (!gr) {
+    const int rc = check_stem_shape(shape);
+    return rc != NODE_OK ? rc : fail(NODE_ERR_NULL, "a required pointer is NULL");
+  }
+  return stem_bwd(shape, prm, x, grad_out, gr, nullptr, ws, ws_bytes, stream, "node_stem_bwd");
+}
+
+int node_stem_bwd_dx(const node_stem_shape* shape, const node_stem_params* prm, const float* x, const float* grad_out,
+                     const node_stem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream) {
+  if (!d_x) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  return stem_bwd(shape, prm, x, grad_out, gr, d_x, ws, ws_bytes, stream, "node_stem_bwd_dx");
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -416,6 +454,34 @@ int check_geom(const node_conv_geom* g) {
   return NODE_OK;
 }
 }  // namespace
+
+// the transposed first layer alone, on NCHW tensors: dy -> NHWC in the workspace, then k_stem_conv0_dgrad
+static int check_dgrad0(const node_stem_shape* sh) {
+  if (!sh) return fail(NODE_ERR_NULL, "shape is NULL");
+  if (sh->n <= 0 || sh->in_ch <= 0 || sh->h < 3 || sh->w < 3) return fail(NODE_ERR_SHAPE, "bad shape");
+  if (sh->in_ch > 3) return fail(NODE_ERR_UNSUPPORTED, "the stem's first layer takes in_ch <= 3 (got %d)", sh->in_ch);
+  if ((size_t)sh->n * sh->h * sh->w * 64 >= ((size_t)1 << 31)) return fail(NODE_ERR_UNSUPPORTED, "stem tensors must stay under 2^31 elements");
+  return NODE_OK;
+}
+
+size_t node_stem_conv0_dgrad_workspace_bytes(const node_stem_shape* shape) {
+  if (check_dgrad0(shape) != NODE_OK) return 0;
+  return (size_t)shape->n * (shape->h - 2) * (shape->w - 2) * 64 * sizeof(float) + 256;
+}
+
+int node_stem_conv0_dgrad(const node_stem_shape* shape, const float* w0, const float* dy, float* d_x, void* ws, size_t ws_bytes,
+                          void* stream) {
+  int rc = check_dgrad0(shape);
+  if (rc != NODE_OK) return rc;
+  if (!w0 || !dy || !d_x || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+  if (ws_bytes < node_stem_conv0_dgrad_workspace_bytes(shape)) return fail(NODE_ERR_WORKSPACE, "workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  launch_stem_from_nchw(dy, (float*)ws, nullptr, 0, shape->n, 64, (shape->h - 2) * (shape->w - 2), st);
+  if ((rc = launch_ok("stem_from_nchw")) != NODE_OK) return rc;
+  launch_stem_conv0_dgrad((const float*)ws, w0, d_x, shape->n, shape->in_ch, shape->h, shape->w, st);
+  return launch_ok("node_stem_conv0_dgrad");
+}
 
 size_t node_stem_conv_workspace_bytes(const node_conv_geom* g) {
   if (check_geom(g) != NODE_OK) return 0;

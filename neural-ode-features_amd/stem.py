@@ -95,18 +95,31 @@ class _StemFn(torch.autograd.Function):
         shape = _lib.NodeStemShape(*ctx.shape_args)
         dev = x.device
         grad_out = grad_out.contiguous()
-        grads = [torch.empty_like(p) for p in ps]
+        # parameter gradients: all sixteen or none (an attack freezes the parameters: the data-gradient chain alone)
+        want_params = any(ctx.needs_input_grad[2:])
+        want_dx = ctx.needs_input_grad[0]     # (only with ResidualStem.input_grad: `fusable` sends any other such input elsewhere)
+        grads = [torch.empty_like(p) for p in ps] if want_params or not want_dx else None
         ws = ctx.ws
+        d_x = None
         with torch.cuda.device(dev):
             wsp = (ws.data_ptr() + 255) & ~255
-            _lib.check(lib.node_stem_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
-                                         C.byref(_struct(grads)), wsp, ctx.nbytes, torch.cuda.current_stream(dev).cuda_stream))
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if want_dx:
+                d_x = torch.empty_like(x)
+                _lib.check(lib.node_stem_bwd_dx(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                                C.byref(_struct(grads)) if grads is not None else None, d_x.data_ptr(), wsp,
+                                                ctx.nbytes, stream))
+            else:
+                _lib.check(lib.node_stem_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                             C.byref(_struct(grads)), wsp, ctx.nbytes, stream))
         _WS[ctx.key] = ws            # free for the next forward of this shape (stream-ordered behind this backward)
         ctx.ws = None
-        return (None, None, *grads)
+        if grads is None:
+            grads = [None] * len(ps)
+        return (d_x, None, *grads)
 
 
-def fusable(seq, x) -> bool:
+def fusable(seq, x, input_grad=False) -> bool:
     """What the library's stem kernels take (node_stem_fwd): fp32 on a HIP device, in_ch <= 3, filters a power of two >= 64,
     images of up to 2400 pixels behind the first layer (the GroupNorm passes hold a (sample, 8 channels) block in LDS);
     anything else -- the 24- and 32-filter toy nets of the tests, 64x64 inputs -- runs the module sequence."""
@@ -114,8 +127,10 @@ def fusable(seq, x) -> bool:
             and min(x.shape[2], x.shape[3]) >= 5 and (x.shape[2] - 2) * (x.shape[3] - 2) <= 2400):
         return False
     ps = _params_of(seq)
-    if x.requires_grad and torch.is_grad_enabled():
-        return False        # the fused backward produces parameter gradients only (saliency / adversarial inputs: module sequence)
+    if x.requires_grad and torch.is_grad_enabled() and not input_grad:
+        # by default the fused backward produces parameter gradients only (saliency / adversarial inputs: module sequence);
+        # ResidualStem.input_grad opts in to node_stem_bwd_dx, which also returns the image's gradient
+        return False
     filters = ps[-1].shape[0] if ps is not None else 0
     # power-of-two filter counts: the GroupNorm passes keep whole groups inside power-of-two channel blocks (192, 384, ... are
     # refused by check_stem_shape, csrc/stem_api.hip)
@@ -125,10 +140,16 @@ def fusable(seq, x) -> bool:
 
 class ResidualStem(nn.Sequential):
     """`nn.Sequential(Conv2d(in_ch, 64, 3, 1), ResBlock(64, 64, 2, conv1x1), ResBlock(64, out_ch, 2, conv1x1))` with the
-    reference's state_dict keys; on a HIP device its forward and backward are the library's (one autograd node)."""
+    reference's state_dict keys; on a HIP device its forward and backward are the library's (one autograd node).
+
+    `input_grad` (default False): with it on, an input that requires a gradient stays on the fused path and the backward
+    returns the image's gradient too (node_stem_bwd_dx; with frozen parameters only the data-gradient chain runs).  Off, such
+    an input runs the module sequence, as it always has.  `nof.attack.bim` switches it on for the attack's duration."""
+
+    input_grad = False
 
     def forward(self, x):
-        if not fusable(self, x):
+        if not fusable(self, x, self.input_grad):
             return super().forward(x)
         ps = _params_of(self)
         if not (torch.is_grad_enabled() and any(p.requires_grad for p in ps)):
