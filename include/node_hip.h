@@ -243,7 +243,15 @@ int node_solve_fwd(const node_shape* shape, const node_params* params,
 /* Backward of torchdiffeq.odeint_adjoint (triggered by train.py:51):
  * y_traj = the forward's y_out, grad_out = dL/dy_out, both [n_t, n, c, h, w].
  * Outputs: grad_y0 [n, c, h, w]; grad_params [node_param_count] flat in
- * parameters() order; grad_t [n_t] or NULL (the reference discards it). */
+ * parameters() order; grad_t [n_t] or NULL (the reference discards it).
+ * grad_t is dL/dt_pts in upstream's `time_vjps` order, in the CALLER's time for an increasing and for a decreasing grid alike:
+ *   grad_t[i] = <f(t_i, y_i), dL/dy_i>  for i >= 1 (exactly 0 for a slice that opts->grad_last_only declares zero),
+ *   grad_t[0] = adj_time, the scalar segment of the augmented state: it starts at 0, loses <f(t_i, y_i), dL/dy_i> at the start
+ *               of every interval [t_i -> t_{i-1}] and is integrated through it with d adj_time / dt = -adj_y . df/dt.
+ * Sign convention: an interval that runs towards smaller t (every interval of an increasing grid) is solved in s = -t with the
+ * dynamics tsign * f(tsign * s, .), tsign = -1, as upstream does; the interval's first stage then holds tsign * f, the dot
+ * product is taken from it and multiplied by tsign again, and the time component of the augmented dynamics carries the same
+ * factor -- so no entry of grad_t changes sign with the direction of the solve (tests/test_gpu_adjoint_time.py). */
 int node_solve_adjoint(const node_shape* shape, const node_params* params,
                        const float* y_traj, const float* grad_out,
                        const float* t_pts, int n_t,

@@ -830,7 +830,11 @@ def solve_last(func, y0, t, rtol, atol, method, adjoint, options=None):
 def odeint_adjoint(func, y0, t, rtol=1e-6, atol=1e-12, method=None, options=None):
     """Drop-in for `torchdiffeq.odeint_adjoint` on the reference's call
     (model.py:359,367).  Returns `[len(t), *y0.shape]`, `out[0] == y0`;
-    gradients flow to `y0` and `func.parameters()` through the HIP adjoint solve."""
+    gradients flow to `y0` and `func.parameters()` through the HIP adjoint solve.
+
+    No gradient reaches a `t` that requires grad: the reference discards it, and so does
+    this surface.  The library computes it all the same -- `solve_adjoint(...,
+    want_grad_t=True)` returns `grad_t` (layout and sign: include/node_hip.h)."""
     return _odeint_impl(func, y0, t, rtol, atol, method, options)
 
 

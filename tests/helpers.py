@@ -647,3 +647,143 @@ def sc_dense_scenario(n):
     dt2, _ = sc_dt_next(st['dt'], 0.05)
     t, dt = st['t'], st['dt']
     return st, [t + 0.3 * dt, t + 0.5 * dt, t + dt, t + dt + 0.5 * dt2, t + 10.0]
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The adjoint's time gradients (tests/test_gpu_adjoint_time.py, tools/adjoint_time_d32.py).
+#
+# node_solve_adjoint's third output, grad_t [n_t], in upstream's `time_vjps` order: grad_t[0] is the integrated adj_time,
+# grad_t[i] = <f(t_i, y_i), dL/dy_i> for i >= 1.  The reference is the oracle's `odeint_adjoint` with a time grid that requires
+# grad.  A case = (shape, grid, method, mode); mode 'replay' forces the step sizes below in both directions (both sides repeat
+# a list's last entry until the interval's end is passed and restart the backward list at every interval, so one list serves
+# any grid and no step lands on a target: every interval ends in dense output), 'free' lets the controller run, rk4 has no
+# step sizes to force.
+# ----------------------------------------------------------------------------------------------------------------------
+AT_FWD_DTS = [0.07, 0.11, 0.13]
+AT_BWD_DTS = [0.06, 0.09, 0.14]
+AT_ALIGN = (1.0, -0.7, 0.5, 0.8)      # c_i: how much of f(t_i, y_i)'s direction slice i of the cotangent carries
+AT_TOL = 1e-3
+AT_SEED = 61
+
+# family -> (shape, what node_describe_dims must say of it): the smallest shape of each kernel family an adjoint solve can take
+AT_FAMILIES = {
+    'small-C': ((2, 16, 4, 4), dict(wino4=0, wgrad_kernel='W2_4', conv_kernel='W1_64')),      # C below one channel tile, units of 4 tiles
+    'fp32': ((3, 32, 8, 8), dict(wino4=0, wgrad_kernel='W2_8', conv_kernel='W1_64')),         # fp32 convolution + fp32 weight gradient
+    'w4-8x8': ((8, 64, 8, 8), dict(wino4=1, w4q=1)),                                          # F(4x4,3x3) pipeline, 8 x 8 states
+    'w4-16x16': ((2, 128, 16, 16), dict(wino4=1, w4q=4)),                                     # ... its 16 x 16 quadrant passes
+}
+AT_GRIDS = [(0.0, 0.3, 0.55, 1.0), (1.0, 0.4, 0.0), (1.0, 0.25), (0.0, 1.0)]
+# (family, grid, method, mode) of every comparison with the oracle
+AT_DOPRI5 = ([(fam, g, 'dopri5', 'replay') for fam in ('small-C', 'fp32') for g in AT_GRIDS] +
+             [(fam, g, 'dopri5', 'replay') for fam in ('w4-8x8', 'w4-16x16') for g in AT_GRIDS[:2]])
+AT_RK4 = [(fam, g, 'rk4', 'fixed') for fam in ('small-C', 'fp32') for g in AT_GRIDS[:2]]
+
+
+# bound on the grad_t error of (method, family): 8 x the family's largest d32 (the fp32 CPU oracle's own distance from the fp64
+# arbiter, tools/adjoint_time_d32.py -> profiles/adjoint_time_grads.txt), rounded up to one significant digit
+AT_GT_TOL = {('dopri5', 'small-C'): 7e-6, ('dopri5', 'fp32'): 8e-6, ('dopri5', 'w4-8x8'): 2e-5, ('dopri5', 'w4-16x16'): 4e-6,
+             ('rk4', 'small-C'): 7e-7, ('rk4', 'fp32'): 2e-6}
+# every grad_t entry is at least this fraction of sum_j ||f_j|| ||g_j|| under the aligned cotangent (measured 0.050 ... 0.27 over the
+# cases; a random cotangent gives ~1e-3): below it the relative bound above would be a bound on a cancelled sum
+AT_MIN_COND = 0.04
+
+
+def at_id(fam, grid, method, mode):
+    return '%s-%s-%s-%s' % (fam, 'x'.join('%d' % d for d in AT_FAMILIES[fam][0]), method, '_'.join('%g' % v for v in grid))
+
+
+_AT_CASES = {}
+
+
+def at_options(method, mode):
+    return {'forced_dts': list(AT_FWD_DTS), 'forced_dts_bwd': list(AT_BWD_DTS)} if (method == 'dopri5' and mode == 'replay') else None
+
+
+def _at_oracle(twin, y, t, g, method, options):
+    """The oracle's adjoint solve with t.requires_grad: dict(out, gy, gp (flat, parameters() order), gt, fwd, bwd)."""
+    from oracle import torchdiffeq_restated as tdq
+    for p in twin.parameters():
+        p.grad = None
+    yo = y.clone().requires_grad_(True)
+    to = t.clone().requires_grad_(True)
+    fs, bs = tdq.SolverStats(), tdq.SolverStats()
+    out = tdq.odeint_adjoint(twin, yo, to, rtol=AT_TOL, atol=AT_TOL, method=method, options=dict(options) if options else None,
+                             fwd_stats=fs, bwd_stats=bs)
+    (out * g).sum().backward()
+    return dict(out=out.detach().cpu(), gy=yo.grad.cpu(), gp=torch.cat([p.grad.reshape(-1) for p in twin.parameters()]).cpu(),
+                gt=to.grad.cpu(), fwd=fs, bwd=bs)
+
+
+def at_err(got, ref):
+    """max_i |got_i - ref_i| / max_i |ref_i| of a time gradient."""
+    got, ref = got.detach().double().cpu().reshape(-1), ref.detach().double().cpu().reshape(-1)
+    return float((got - ref).abs().max() / ref.abs().max())
+
+
+def adjoint_time_case(shape, grid, method='dopri5', mode='replay', arbiter=True):
+    """Inputs and references of one case, computed once per process and left unchanged.
+
+    Parameters: make_func(C, AT_SEED, kink_free=True).  The grid is rounded to fp32 (the ABI takes `float` times); the fp64 arbiter
+    is given those values widened.  The cotangent makes grad_t WELL CONDITIONED: with a random dL/dy_i, <f_i, g_i> is a
+    near-cancelling sum (|grad_t| ~ 0.2 against sum ||f_i|| ||g_i|| ~ 130) and a relative bound on it means nothing, so the fp32
+    CPU oracle's forward solve supplies y(t_i), and g_i = noise_i + c_i ||noise_i|| f_i / ||f_i|| with c = AT_ALIGN and
+    noise_i = randn / sqrt(C H W): every <f_i, g_i> is then a fixed fraction of ||f_i|| ||g_i||.
+
+    Returns dict(shape, times (host floats of the fp32 grid), y, g [T, N, C, H, W], options, o32 = the fp32 CPU oracle's solve,
+    f64 = the fp64 arbiter's on _arbiter_device() (arbiter=True), d32 = at_err(o32 grad_t, f64 grad_t), cond = min_i |grad_t_i| /
+    sum_j ||f_j|| ||g_j|| over the arbiter's (else the oracle's) grad_t)."""
+    from oracle import torchdiffeq_restated as tdq
+    key = (tuple(shape), tuple(grid), method, mode)
+    hit = _AT_CASES.get(key)
+    if hit is not None and (hit['f64'] is not None or not arbiter):
+        return hit
+    N, C, H, W = shape
+    T = len(grid)
+    assert T <= len(AT_ALIGN)
+    _, twin = make_func(C, seed=AT_SEED, kink_free=True)
+    gen = torch.Generator().manual_seed(AT_SEED + 1)
+    y = torch.randn(N, C, H, W, generator=gen)
+    noise = torch.randn(T, N, C, H, W, generator=gen) / (C * H * W) ** 0.5
+    t32 = torch.tensor(grid, dtype=torch.float32)
+    options = at_options(method, mode)
+    fopts = {'forced_dts': list(options['forced_dts'])} if options else None
+    with torch.no_grad():
+        traj = tdq.odeint(twin, y, t32, rtol=AT_TOL, atol=AT_TOL, method=method, options=fopts)
+        fs = torch.stack([twin(t32[i], traj[i]) for i in range(T)])
+    g = torch.stack([noise[i] + AT_ALIGN[i] * noise[i].norm() * fs[i] / fs[i].norm() for i in range(T)])
+    o32 = _at_oracle(twin, y, t32, g, method, options)
+    f64 = None
+    if arbiter:
+        dev = _arbiter_device()
+        tw = copy.deepcopy(twin).to(torch.float64).to(dev)
+        f64 = _at_oracle(tw, y.to(torch.float64).to(dev), t32.to(torch.float64).to(dev), g.to(torch.float64).to(dev), method, options)
+    ref_gt = (f64 or o32)['gt'].double()
+    scale = float(sum(fs[i].double().norm() * g[i].double().norm() for i in range(T)))
+    case = dict(shape=tuple(shape), times=[float(v) for v in t32.tolist()], y=y, g=g, method=method, options=options, o32=o32, f64=f64,
+                d32=at_err(o32['gt'], f64['gt']) if f64 else None, cond=float(ref_gt.abs().min()) / scale)
+    _AT_CASES[key] = case
+    return case
+
+
+_AT_FUNCS = {}
+
+
+def at_hip_solve(case, want_grad_t=True, grad_last_only=False, grad_out=None):
+    """The library's forward and adjoint solve of a case through integrate.solve_forward / solve_adjoint (no autograd in between:
+    the autograd surface discards grad_t).  `grad_out` replaces the case's cotangent; with `grad_last_only` it is the last slice
+    alone.  Returns dict(out, gy, gp, gt (None unless wanted), fwd, bwd (the solves' statistics), pair (node_w4_pair_stats))."""
+    from neural_ode_features_amd import _lib, integrate
+    C = case['shape'][1]
+    if C not in _AT_FUNCS:
+        _AT_FUNCS[C] = make_func(C, seed=AT_SEED, device='cuda', kink_free=True)[0]
+    f = _AT_FUNCS[C]
+    rec = integrate.Recognised(f)
+    mid = _lib.METHODS[case['method']]
+    g = case['g'] if grad_out is None else grad_out
+    with tune_env(NODE_TUNE_W4_STATS='1'):
+        out, fs = integrate.solve_forward(rec, rec.params, case['y'].cuda(), case['times'], AT_TOL, AT_TOL, mid, case['options'])
+        gy, gp, gt, bs = integrate.solve_adjoint(rec, rec.params, out, g.cuda(), case['times'], AT_TOL, AT_TOL, mid, case['options'],
+                                                 want_grad_t=want_grad_t, grad_last_only=grad_last_only)
+        st = (ctypes.c_int32 * 4)()
+        _lib.check(_lib.load().node_w4_pair_stats(st))
+    return dict(out=out.cpu(), gy=gy.cpu(), gp=gp.cpu(), gt=gt.cpu() if gt is not None else None, fwd=fs, bwd=bs, pair=list(st))
