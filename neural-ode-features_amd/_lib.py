@@ -26,6 +26,7 @@ ERRORS = {
     -4: 'NODE_ERR_WORKSPACE', -5: 'NODE_ERR_MAX_STEPS', -6: 'NODE_ERR_NONFINITE',
     -7: 'NODE_ERR_DT_UNDERFLOW', -8: 'NODE_ERR_HIP', -9: 'NODE_ERR_ARG',
 }
+NODE_ERR_UNSUPPORTED = -3
 
 EXPORTS = [
     'node_abi_version', 'node_last_error', 'node_param_count', 'node_workspace_bytes', 'node_solve_is_resident',
@@ -356,3 +357,8 @@ def load():
 def check(rc):
     if rc != 0:
         raise NodeHipError(rc, load().node_last_error().decode('utf-8', 'replace'))
+
+
+def unsupported():
+    """A workspace-size query returned 0: the library refuses the geometry and has said why."""
+    raise NodeHipError(NODE_ERR_UNSUPPORTED, load().node_last_error().decode('utf-8', 'replace'))

@@ -28,14 +28,14 @@ import warnings
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, workspace
 
 DEFAULT_EPS = 1e-5
 DEFAULT_MAX_ITER = 100
 MAX_D = 280
 PROBLEM = np.dtype([('fold', '<i4'), ('cls', '<i4'), ('c', '<f4')])
 RESULT = np.dtype([('iterations', '<i4'), ('converged', '<i4'), ('grad_ratio', '<f8')])
-_WS = {}
+_WS = workspace.Scratch()      # the solver's scratch, one buffer per (device, stream)
 
 
 def stratified_folds(labels, k=5):
@@ -75,15 +75,6 @@ def problem_table(folds, classes, Cs):
     t = np.empty(len(Cs), PROBLEM)
     t['fold'], t['cls'], t['c'] = folds, classes, Cs
     return t
-
-
-def _workspace(device, nbytes):
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes + 256:
-        buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        _WS[key] = buf
-    return buf
 
 
 def _check_x(x):
@@ -139,10 +130,9 @@ def _fit(x, lab, fold, table, eps, max_iter):
     res = torch.empty(p * RESULT.itemsize, dtype=torch.uint8, device=dev)
     nbytes = lib.node_svm_workspace_bytes(n, d, p)
     if nbytes == 0:
-        raise _lib.NodeHipError(-3, lib.node_last_error().decode('utf-8', 'replace'))
+        _lib.unsupported()
     with torch.cuda.device(dev):
-        ws = _workspace(dev, nbytes)
-        ptr = (ws.data_ptr() + 255) & ~255
+        ptr = workspace.aligned_ptr(_WS.take(dev, nbytes))
         _lib.check(lib.node_svm_fit(n, d, p, x.data_ptr(), lab.data_ptr(), fold.data_ptr(), prob.data_ptr(), float(eps),
                                     int(max_iter), w.data_ptr(), res.data_ptr(), ptr, nbytes,
                                     torch.cuda.current_stream(dev).cuda_stream))

@@ -27,14 +27,9 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import _lib
+from . import _lib, workspace
 
 _GUESS: Dict[tuple, int] = {}       # steps the last solve of the same problem took (enqueued before the first read-back)
-
-
-def _aligned(nbytes, device):
-    buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-    return buf, (buf.data_ptr() + 255) & ~255
 
 
 class FlatSolve:
@@ -66,8 +61,8 @@ class FlatSolve:
     def _reserve(self, n_targets):
         if self._ws is None or n_targets > self.n_targets:
             nbytes = self.lib.node_flat_workspace_bytes(int(n_targets))
-            self._ws, base = _aligned(nbytes, self.device)
-            self.s.ws, self.s.ws_bytes = base, nbytes
+            self._ws = workspace.alloc(nbytes, self.device)      # owned by this solve for its whole life
+            self.s.ws, self.s.ws_bytes = workspace.aligned_ptr(self._ws), nbytes
         self.n_targets = n_targets
         self.s.n_targets = n_targets
 

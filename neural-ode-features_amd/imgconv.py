@@ -20,22 +20,19 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, workspace
 
-_WS = {}
+_WS = workspace.Scratch()
 
 
 def _workspace(lib, shape, shape_args, dev):
-    """The backward's scratch, one per (device, stream, shape): it carries nothing between calls, and calls on one stream are
-    ordered.  Autograd runs a node's backward on its forward's stream, so the buffer the forward made is the one the backward finds."""
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream) + tuple(shape_args)
-    ws = _WS.get(key)
-    if ws is None:
-        nbytes = lib.node_imgconv_workspace_bytes(C.byref(shape))
-        if nbytes == 0:
-            raise _lib.NodeHipError(-3, lib.node_last_error().decode())
-        ws = _WS[key] = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    return ws
+    """The backward's scratch (aligned pointer, bytes), one per (device, stream, shape): it carries nothing between calls, and calls
+    on one stream are ordered.  Autograd runs a node's backward on its forward's stream, so the buffer the forward made is the one
+    the backward finds."""
+    nbytes = lib.node_imgconv_workspace_bytes(C.byref(shape))
+    if nbytes == 0:
+        _lib.unsupported()
+    return workspace.aligned_ptr(_WS.take(dev, nbytes, *shape_args)), nbytes
 
 
 class _ImgConvFn(torch.autograd.Function):
@@ -78,10 +75,10 @@ class _ImgConvFn(torch.autograd.Function):
             dw = torch.empty_like(w)
             db = torch.empty(w.shape[0], dtype=torch.float32, device=dev) if ctx.has_bias else None
             dx = torch.empty_like(x) if want_x else None
-            ws = _workspace(lib, shape, ctx.shape_args, dev)
+            ws, nbytes = _workspace(lib, shape, ctx.shape_args, dev)
             _lib.check(lib.node_imgconv_bwd(C.byref(shape), x.data_ptr(), w.data_ptr(), grad_y.data_ptr(), dw.data_ptr(),
                                             db.data_ptr() if db is not None else None, dx.data_ptr() if dx is not None else None,
-                                            ws.data_ptr(), ws.numel(), torch.cuda.current_stream(dev).cuda_stream))
+                                            ws, nbytes, torch.cuda.current_stream(dev).cuda_stream))
         return dx, dw, db, None
 
 

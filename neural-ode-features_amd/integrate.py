@@ -1,8 +1,10 @@
 """`odeint` / `odeint_adjoint` -- the torchdiffeq surface the reference imports
 (`/root/reference/model.py:3`) and calls (`model.py:367`), backed by the HIP
-library.  Host logic only: argument checking, recognising the conv `ODEfunc`
-(`model.py:326-348`), handing raw device pointers to the C ABI, and wiring the
-adjoint into autograd.  All arithmetic happens in libnode_hip.so.
+library.  Host logic only: argument checking, handing raw device pointers to the
+C ABI, and wiring the adjoint into autograd.  All arithmetic happens in
+libnode_hip.so.  Recognising the conv `ODEfunc` (`model.py:326-348`) lives in
+recognise.py, deferred completion of a training step's solves in deferred.py,
+the caller-owned workspace in workspace.py.
 
 No CPU path, no path through `oracle/`: CPU tensors and non-fp32 tensors raise.
 Dynamics that are not the reference's Conv-GroupNorm-ReLU `ODEfunc` (any other
@@ -13,101 +15,15 @@ operations, the library's own device-resident step controller around it.
 from __future__ import annotations
 
 import ctypes as C
-import itertools
-import os
 import weakref
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional
 
 import torch
 from torch import nn
 
-from . import _lib
-
-PARAM_ATTRS = [
-    ('norm1', 'weight'), ('norm1', 'bias'), ('conv1', 'weight'), ('conv1', 'bias'),
-    ('norm2', 'weight'), ('norm2', 'bias'), ('conv2', 'weight'), ('conv2', 'bias'),
-    ('norm3', 'weight'), ('norm3', 'bias'),
-]
-
-
-class Recognised:
-    """The ten parameters + GroupNorm config of a conv ODEfunc (duck-typed so the
-    reference's own `model.ODEfunc` instance is accepted unchanged)."""
-
-    def __init__(self, func: nn.Module):
-        def conv_of(m):
-            layer = getattr(m, '_layer', None)
-            if not isinstance(layer, nn.Conv2d):
-                raise NotImplementedError('ConcatConv2d with a plain nn.Conv2d `_layer` expected')
-            if layer.kernel_size != (3, 3) or layer.stride != (1, 1) or layer.padding != (1, 1) \
-                    or layer.dilation != (1, 1) or layer.groups != 1 or layer.bias is None:
-                raise NotImplementedError('only Conv2d(dim+1, dim, 3, 1, 1, bias=True) dynamics are accelerated')
-            return layer
-
-        for name in ('norm1', 'conv1', 'norm2', 'conv2', 'norm3'):
-            if not hasattr(func, name):
-                raise NotImplementedError(
-                    'neural-ode-features_amd accelerates the reference ODEfunc (model.py:326-348) only; '
-                    '%s has no attribute %r' % (type(func).__name__, name))
-        norms = [func.norm1, func.norm2, func.norm3]
-        for nrm in norms:
-            if not isinstance(nrm, nn.GroupNorm):
-                raise NotImplementedError("only norm='group' dynamics are accelerated (BatchNorm couples samples)")
-            if not nrm.affine:
-                raise NotImplementedError('GroupNorm must be affine')
-        c1, c2 = conv_of(func.conv1), conv_of(func.conv2)
-        dim = norms[0].num_channels
-        for nrm in norms:
-            if nrm.num_channels != dim or nrm.num_groups != norms[0].num_groups or nrm.eps != norms[0].eps:
-                raise NotImplementedError('the three GroupNorms must share channels / groups / eps')
-        for cv in (c1, c2):
-            if cv.in_channels != dim + 1 or cv.out_channels != dim:
-                raise NotImplementedError('ConcatConv2d(dim, dim) expected')
-        self.dim, self.groups, self.eps = dim, norms[0].num_groups, float(norms[0].eps)
-        self.params: List[torch.Tensor] = [
-            func.norm1.weight, func.norm1.bias, c1.weight, c1.bias,
-            func.norm2.weight, func.norm2.bias, c2.weight, c2.bias,
-            func.norm3.weight, func.norm3.bias]
-        # must equal func.parameters() order: defines the flat-gradient layout (SURVEY.md 8b)
-        own = list(func.parameters())
-        if len(own) != 10 or any(a is not b for a, b in zip(own, self.params)):
-            raise NotImplementedError('ODEfunc.parameters() is not the expected ten tensors in reference order')
-
-
-# Recognised(func) walks the module tree (named_modules, parameters): ~25 us per call, once per solve.  The result is remembered per
-# func OBJECT (weakly) together with the identities it was built from -- the five sub-modules, the two conv layers, the ten parameter
-# objects, the counts of func's own entries -- and rebuilt when any of them is another object (a replaced layer or parameter, a
-# `load_state_dict` keeps the objects and needs nothing).
-_REC_SEEN: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
-
-
-def _rec_signature(func):
-    try:      # (straight through the modules' own dicts: nn.Module.__getattr__ costs ~0.4 us per lookup, this runs once per solve)
-        m = func._modules
-        n1, c1, n2, c2, n3 = m['norm1'], m['conv1'], m['norm2'], m['conv2'], m['norm3']
-        l1, l2 = c1._modules['_layer'], c2._modules['_layer']
-        p1, q1, p2, q2, p3 = n1._parameters, l1._parameters, n2._parameters, l2._parameters, n3._parameters
-        return (id(n1), id(c1), id(n2), id(c2), id(n3), id(l1), id(l2),
-                id(p1['weight']), id(p1['bias']), id(q1['weight']), id(q1['bias']), id(p2['weight']), id(p2['bias']),
-                id(q2['weight']), id(q2['bias']), id(p3['weight']), id(p3['bias']), n1.num_groups, n1.eps, len(m), len(func._parameters))
-    except (AttributeError, KeyError):
-        return None
-
-
-def recognised(func: nn.Module) -> Recognised:
-    """Recognised(func), remembered per object; raises NotImplementedError like the constructor."""
-    sig = _rec_signature(func)
-    if sig is not None:
-        try:
-            hit = _REC_SEEN.get(func)
-        except TypeError:       # (an unhashable / non-weakly-referenceable object: no cache)
-            hit, sig = None, None
-        if hit is not None and hit[0] == sig:
-            return hit[1]
-    rec = Recognised(func)
-    if sig is not None:
-        _REC_SEEN[func] = (sig, rec)
-    return rec
+from . import _lib, workspace
+from .deferred import Deferred, DeferredLoop, _func_token  # noqa: F401
+from .recognise import Recognised, recognised  # noqa: F401
 
 
 def _method_id(method) -> int:
@@ -162,22 +78,7 @@ def _host_times(t: torch.Tensor) -> List[float]:
     return list(vals)
 
 
-_WS: Dict[Tuple[int, int], torch.Tensor] = {}
-
-
-def _workspace(device: torch.device, nbytes: int) -> torch.Tensor:
-    """Caller-owned device workspace (the library never allocates device memory)."""
-    key = (device.index if device.index is not None else torch.cuda.current_device(),
-           torch.cuda.current_stream(device).cuda_stream)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        _WS[key] = buf
-    return buf
-
-
-def _aligned_ptr(buf: torch.Tensor) -> int:
-    return (buf.data_ptr() + 255) & ~255
+_WS = workspace.Scratch()      # the solves' workspace, one buffer per (device, stream)
 
 
 def _check_state(y0: torch.Tensor, any_rank: bool = False):
@@ -211,10 +112,7 @@ def _fused_plan(func, y0, method_id, adjoint, n_t):
         return None
     if not GENERIC_FALLBACK:
         return rec
-    n, c, h, w = y0.shape
-    if c != rec.dim:
-        raise ValueError('state has %d channels but the ODEfunc was built for %d' % (c, rec.dim))
-    shape = _lib.NodeShape(n, c, h, w, rec.groups, rec.eps)
+    shape = _shape_struct(y0, rec)
     return rec if _lib.load().node_workspace_bytes(C.byref(shape), method_id, 1 if adjoint else 0, n_t) != 0 else None
 
 
@@ -225,7 +123,7 @@ def _shape_struct(y0: torch.Tensor, rec: Recognised) -> _lib.NodeShape:
     return _lib.NodeShape(n, c, h, w, rec.groups, rec.eps)
 
 
-def _params_struct(params: List[torch.Tensor], device) -> Tuple[_lib.NodeParams, List[torch.Tensor]]:
+def _params_struct(params: List[torch.Tensor], device) -> _lib.NodeParams:
     keep = []
     ptrs = []
     for p in params:
@@ -236,7 +134,33 @@ def _params_struct(params: List[torch.Tensor], device) -> Tuple[_lib.NodeParams,
             q = q.contiguous()
         keep.append(q)
         ptrs.append(q.data_ptr())
-    return _lib.NodeParams(*ptrs), keep
+    struct = _lib.NodeParams(*ptrs)
+    struct.keep = keep         # the struct holds raw addresses: the tensors behind them live as long as it does
+    return struct
+
+
+def _marshal(rec: Recognised, params: List[torch.Tensor], y: torch.Tensor, query, *query_args):
+    """What the five entry points hand the library besides their own arguments, made in one place.  Returns the shape
+    struct of the state `y` (channels checked against `rec`) and `call`.
+
+    `call(entry, *args)` runs `entry(shape, params, *args, workspace, its bytes, stream)` on `y`'s device and current stream,
+    and raises on a non-zero return code.  The workspace is sized by `query(shape, *query_args)`; 0 bytes means the library
+    refuses the geometry, which raises NODE_ERR_UNSUPPORTED here on the host."""
+    dev = y.device
+    shape = _shape_struct(y, rec)
+    pstruct = _params_struct(params, dev)
+
+    def call(entry, *args):
+        with torch.cuda.device(dev):
+            ws_bytes = query(C.byref(shape), *query_args)
+            if ws_bytes == 0:
+                _lib.unsupported()
+            ws = _WS.take(dev, ws_bytes)
+            rc = entry(C.byref(shape), C.byref(pstruct), *args, workspace.aligned_ptr(ws), ws_bytes,
+                       torch.cuda.current_stream(dev).cuda_stream)
+        _lib.check(rc)
+
+    return shape, call
 
 
 def _global_norm_group(options: Optional[dict]):
@@ -321,25 +245,14 @@ def solve_forward(rec: Recognised, params: List[torch.Tensor], y0: torch.Tensor,
                   rtol: float, atol: float, method_id: int, options: Optional[dict], blind: Optional[tuple] = None):
     lib = _lib.load()
     y0c = y0.detach().contiguous()
-    shape = _shape_struct(y0c, rec)
-    pstruct, keep_p = _params_struct(params, y0c.device)
     n_t = len(times)
-    with torch.cuda.device(y0c.device):
-        ws_bytes = lib.node_workspace_bytes(C.byref(shape), method_id, 0, n_t)
-        if ws_bytes == 0:
-            raise _lib.NodeHipError(-3, lib.node_last_error().decode())
-        ws = _workspace(y0c.device, ws_bytes)
-        out = torch.empty((n_t,) + tuple(y0c.shape), dtype=torch.float32, device=y0c.device)
-        tarr = (C.c_float * n_t)(*times)
-        stats = _lib.NodeStats()
-        opts, keep_o = _opts_struct(options, 'forced_dts', blind, device=y0c.device)
-        rc = lib.node_solve_fwd(C.byref(shape), C.byref(pstruct), y0c.data_ptr(), tarr, n_t,
-                                float(rtol), float(atol), method_id,
-                                C.byref(opts) if opts is not None else None,
-                                out.data_ptr(), C.byref(stats), _aligned_ptr(ws), ws_bytes,
-                                torch.cuda.current_stream(y0c.device).cuda_stream)
-    _lib.check(rc)
-    del keep_p
+    _, call = _marshal(rec, params, y0c, lib.node_workspace_bytes, method_id, 0, n_t)
+    out = torch.empty((n_t,) + tuple(y0c.shape), dtype=torch.float32, device=y0c.device)
+    tarr = (C.c_float * n_t)(*times)
+    stats = _lib.NodeStats()
+    opts, keep_o = _opts_struct(options, 'forced_dts', blind, device=y0c.device)
+    call(lib.node_solve_fwd, y0c.data_ptr(), tarr, n_t, float(rtol), float(atol), method_id,
+         C.byref(opts) if opts is not None else None, out.data_ptr(), C.byref(stats))
     return out, _stats_dict(stats, keep_o)
 
 
@@ -351,30 +264,17 @@ def solve_adjoint(rec: Recognised, params: List[torch.Tensor], y_traj: torch.Ten
     y_traj = y_traj.detach().contiguous()
     grad_out = grad_out.detach().contiguous()
     dev = y_traj.device
-    shape = _shape_struct(y_traj[0], rec)
-    pstruct, keep_p = _params_struct(params, dev)
     n_t = len(times)
-    with torch.cuda.device(dev):
-        ws_bytes = lib.node_workspace_bytes(C.byref(shape), method_id, 1, n_t)
-        if ws_bytes == 0:
-            raise _lib.NodeHipError(-3, lib.node_last_error().decode())
-        ws = _workspace(dev, ws_bytes)
-        P = lib.node_param_count(C.byref(shape))
-        grad_y0 = torch.empty_like(y_traj[0])
-        grad_p = torch.empty(P, dtype=torch.float32, device=dev)
-        grad_t = torch.empty(n_t, dtype=torch.float32, device=dev) if want_grad_t else None
-        tarr = (C.c_float * n_t)(*times)
-        stats = _lib.NodeStats()
-        opts, keep_o = _opts_struct(options, 'forced_dts_bwd', blind, grad_last_only, device=dev)
-        rc = lib.node_solve_adjoint(C.byref(shape), C.byref(pstruct), y_traj.data_ptr(), grad_out.data_ptr(),
-                                    tarr, n_t, float(rtol), float(atol), method_id,
-                                    C.byref(opts) if opts is not None else None,
-                                    grad_y0.data_ptr(), grad_p.data_ptr(),
-                                    grad_t.data_ptr() if grad_t is not None else None,
-                                    C.byref(stats), _aligned_ptr(ws), ws_bytes,
-                                    torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc)
-    del keep_p
+    shape, call = _marshal(rec, params, y_traj[0], lib.node_workspace_bytes, method_id, 1, n_t)
+    grad_y0 = torch.empty_like(y_traj[0])
+    grad_p = torch.empty(lib.node_param_count(C.byref(shape)), dtype=torch.float32, device=dev)
+    grad_t = torch.empty(n_t, dtype=torch.float32, device=dev) if want_grad_t else None
+    tarr = (C.c_float * n_t)(*times)
+    stats = _lib.NodeStats()
+    opts, keep_o = _opts_struct(options, 'forced_dts_bwd', blind, grad_last_only, device=dev)
+    call(lib.node_solve_adjoint, y_traj.data_ptr(), grad_out.data_ptr(), tarr, n_t, float(rtol), float(atol), method_id,
+         C.byref(opts) if opts is not None else None, grad_y0.data_ptr(), grad_p.data_ptr(),
+         grad_t.data_ptr() if grad_t is not None else None, C.byref(stats))
     return grad_y0, grad_p, grad_t, _stats_dict(stats, keep_o)
 
 
@@ -385,327 +285,38 @@ def solve_backprop(rec: Recognised, params: List[torch.Tensor], y0: torch.Tensor
     lib = _lib.load()
     y0 = y0.detach().contiguous()
     grad_out = grad_out.detach().contiguous()
-    dev = y0.device
-    shape = _shape_struct(y0, rec)
-    pstruct, keep_p = _params_struct(params, dev)
     n_t = len(times)
     n_steps = len(step_dts) if method_id == _lib.METHOD_DOPRI5 else n_t - 1
-    with torch.cuda.device(dev):
-        ws_bytes = lib.node_backprop_workspace_bytes(C.byref(shape), method_id, n_t, n_steps)
-        if ws_bytes == 0:
-            raise _lib.NodeHipError(-3, lib.node_last_error().decode())
-        ws = _workspace(dev, ws_bytes)
-        grad_y0 = torch.empty_like(y0)
-        grad_p = torch.empty(lib.node_param_count(C.byref(shape)), dtype=torch.float32, device=dev)
-        tarr = (C.c_float * n_t)(*times)
-        darr = (C.c_double * max(1, len(step_dts)))(*step_dts)
-        rc = lib.node_solve_backprop(C.byref(shape), C.byref(pstruct), y0.data_ptr(), tarr, n_t, darr, n_steps,
-                                     float(rtol), float(atol), method_id,
-                                     grad_out.data_ptr(), grad_y0.data_ptr(), grad_p.data_ptr(), _aligned_ptr(ws), ws_bytes,
-                                     torch.cuda.current_stream(dev).cuda_stream)
-    _lib.check(rc)
-    del keep_p
+    shape, call = _marshal(rec, params, y0, lib.node_backprop_workspace_bytes, method_id, n_t, n_steps)
+    grad_y0 = torch.empty_like(y0)
+    grad_p = torch.empty(lib.node_param_count(C.byref(shape)), dtype=torch.float32, device=y0.device)
+    tarr = (C.c_float * n_t)(*times)
+    darr = (C.c_double * max(1, len(step_dts)))(*step_dts)
+    call(lib.node_solve_backprop, y0.data_ptr(), tarr, n_t, darr, n_steps, float(rtol), float(atol), method_id,
+         grad_out.data_ptr(), grad_y0.data_ptr(), grad_p.data_ptr())
     return grad_y0, grad_p
 
 
-class Deferred:
-    """Deferred completion of the solves of a training step: keep the queue fed across the solver.
-
-    A dopri5 solve normally ends with one read-back of the device controller (did the steps enqueued finish the
-    interval?), and the host dispatches everything behind it only afterwards -- the GPU idles while PyTorch launches
-    the head, and again while it launches the stem's backward.  With deferred completion enabled, a solve whose step
-    count is known from the previous iteration enqueues exactly that many steps and returns at once; whether they
-    were the steps needed is written by the device into a record, and a MISS (the interval unfinished after them, or an
-    error status; finishing EARLY is no miss -- the steps past the end return at once) bumps the device flag
-    `miss_flag`.  The output of a missed solve is its y0 (the trajectory buffer is pre-filled), and every number
-    computed from it -- loss, accuracy -- belongs to a step whose update was skipped: `step_verdicts()` lists which.  Nothing that commits results may run unconditionally:
-    `optim.FusedSGD.skip_flag = deferred.miss_flag` predicates the parameter update on the device, so a step with a
-    miss changes nothing (under data parallelism the flag rides in the reducer's last bucket, so every rank skips
-    together).  The host looks at a record one iteration later, when it is long complete: the true step count in it
-    becomes the next guess; a miss makes the next solve of that kind run with a read-back again.  While a solve's
-    count is still moving one spare step is enqueued, so only a count that jumps by two or more is a miss.
-
-        deferred = integrate.Deferred(device)        # opt-in; the drop-in API is unaffected while none is active
-        opt.use_deferred(deferred)                   # FusedSGD: the update is predicated on the flag and zeroes it
-        with deferred:                               # (nothing runs blind in a scope no optimizer was armed with)
-            for x, y in loader:
-                loss = F.cross_entropy(model(x), y); loss.backward(); opt.step(); opt.zero_grad()
-        deferred.resolve()                           # -> number of steps whose update was skipped
-
-    `func.nfe` advances by the predicted count at once and is corrected when the record is read (sums over an
-    epoch are exact); `last_*_stats` of a deferred solve hold the prediction."""
-
-    active = None      # the instance whose `with` block is open
-    # How many steps to enqueue for a solve whose true count nobody knows yet.  A step past the end of the interval returns
-    # at its first instruction in every kernel, but its ~40 launches still cost ~0.1 ms; a miss costs the iteration and
-    # (DeferredLoop) the repetition of two batches: ~150x more.  So: enqueue the LARGEST count of the last HIST solves of
-    # this kind (a count that wobbles by one between iterations then wastes half a step on average; a count that DROPS is
-    # followed after HIST iterations), plus ONE spare step whenever a larger count is not unlikely:
-    #   * the history is short (CALM);
-    #   * the last solve overshot the end of its interval by less than FRAGILE of its last step (the record carries the
-    #     last step: node_step_record.t_prev / dt_used) -- step sizes that come out a few percent smaller on the next batch
-    #     then need one step more;
-    #   * a count above everything in the history was seen within the last QUIET solves.
-    # Margins: FRAGILE 0.15 / QUIET 16 in round 4; the measured sweep on the cfg-3 bench loop (profiles/r04_deferred_policy_cfg3.txt)
-    # has 0.05 / 8 at +1.3 % images/s with 0 misses in 200 steps, soaked again in round 5 (profiles/r05_deferred_soak_cfg3.txt).
-    # Round 3 enqueued last count + 1 until eight exact predictions in a row -- at tol 1e-5 that never happened, and every
-    # solve carried one or two dead steps (profiles/r03_r_cfg3_steps.txt: 29 dead component GEMMs per step).
-    HIST = int(os.environ.get('NODE_DEFERRED_HIST', 8))
-    CALM = 4
-    FRAGILE = float(os.environ.get('NODE_DEFERRED_FRAGILE', 0.05))      # (environment: A/B measurements, tools/deferred_soak.py)
-    QUIET = int(os.environ.get('NODE_DEFERRED_QUIET', 8))
-
-    def __init__(self, device):
-        self.device = torch.device(device)
-        self.miss_flag = torch.zeros(1, dtype=torch.float32, device=self.device)
-        self.guess: Dict[tuple, Optional[int]] = {}
-        self.calm: Dict[tuple, int] = {}          # solves of a key since its history was last reset
-        self.hist: Dict[tuple, List[int]] = {}    # true step counts of the last HIST solves of a key
-        self.fragile: Dict[tuple, bool] = {}      # the last solve of a key barely reached the end of its interval
-        self.quiet: Dict[tuple, int] = {}         # solves of a key since one needed more steps than any in its history
-        self.pending: Dict[tuple, tuple] = {}
-        self._seq: Dict[tuple, int] = {}
-        self.records: Dict[tuple, tuple] = {}
-        self.misses = 0
-        self.blind_solves = 0
-        self.dead_steps = 0        # steps enqueued past the end of their interval (read from the records)
-        self.verdicts: List[tuple] = []   # (blind solve index, key kind, missed?) in the order the records were read
-        self.armed = False         # set by FusedSGD.use_deferred: without a predicated commit point nothing runs blind
-        self._last_enqueued: Dict[tuple, int] = {}
-
-    def __enter__(self):
-        Deferred.active = self
-        return self
-
-    def __exit__(self, *exc):
-        Deferred.active = None
-        return False
-
-    def _buffers(self, key):
-        b = self.records.get(key)
-        if b is None:
-            n = C.sizeof(_lib.NodeStepRecord)
-            b = (torch.zeros(n, dtype=torch.uint8, device=self.device), torch.zeros(n, dtype=torch.uint8).pin_memory(),
-                 torch.cuda.Event())
-            self.records[key] = b
-        return b
-
-    def plan(self, key, func=None):
-        """Steps to enqueue blind for `key`, or None for a solve with a read-back.  Looks first at the record the
-        previous blind solve of this key left (one iteration old: complete): its true step count becomes the new
-        guess (and corrects `func.nfe`, which was advanced by the guess), a miss sends the next solve back to a
-        read-back.  While a key's count is still moving, ONE spare step is enqueued (a step past the end of the
-        interval returns at once on the device: ~0.1 ms of launches) so that a count that grows by one is no miss."""
-        pend = self.pending.pop(key, None)
-        if pend is not None:
-            guessed, fref, enqueued = pend
-            if func is None and fref is not None:
-                func = fref()
-            dev, host, event = self._buffers(key)
-            event.synchronize()
-            r = _lib.NodeStepRecord.from_buffer_copy(bytes(host.numpy().tobytes()))
-            self.verdicts.append((self._seq.pop(key, -1), key[0], bool(r.miss)))
-            if len(self.verdicts) > 4096:
-                del self.verdicts[:2048]
-            if r.miss:
-                self.misses += 1
-                self.guess[key] = None
-                self.calm[key] = 0
-                self.hist[key] = []
-            else:
-                if func is not None and r.steps != guessed:
-                    func.nfe = getattr(func, 'nfe', 0) + 6 * (r.steps - guessed)    # late, but sums stay exact
-                self.dead_steps += max(0, enqueued - int(r.steps))
-                # solver time runs upwards in both directions (a solve towards smaller t integrates -t): how far past the
-                # end of the interval did the last step land, in units of that step?
-                end = key[-1][-1] if key[0] == 'fwd' else -key[-1][0]
-                self.fragile[key] = bool(r.dt_used > 0.0 and (r.t - end) < self.FRAGILE * r.dt_used)
-                self._observe(key, int(r.steps))
-        g = self.guess.get(key)
-        if not g or not self.armed:
-            return None
-        return g, self._enqueue(key)
-
-    def _observe(self, key, steps):
-        h = self.hist.setdefault(key, [])
-        self.quiet[key] = 0 if (h and int(steps) > max(h)) else self.quiet.get(key, self.QUIET) + 1
-        h.append(int(steps))
-        del h[:-self.HIST]
-        self.calm[key] = self.calm.get(key, 0) + 1
-        self.guess[key] = int(steps)
-
-    def _spare(self, key):
-        """One spare step while a count above the history's maximum is not unlikely (see the class constants)."""
-        h = self.hist.get(key) or []
-        return len(h) < self.CALM or self.fragile.get(key, False) or self.quiet.get(key, self.QUIET) < self.QUIET
-
-    def _enqueue(self, key):
-        h = self.hist.get(key) or [self.guess[key]]
-        return max(h) + (1 if self._spare(key) else 0)
-
-    def blind_args(self, key, enqueue):
-        dev, _, _ = self._buffers(key)
-        self._last_enqueued[key] = int(enqueue)
-        return (enqueue, dev, self.miss_flag)
-
-    def launched(self, key, guessed, func=None):
-        dev, host, event = self._buffers(key)
-        host.copy_(dev, non_blocking=True)
-        event.record(torch.cuda.current_stream(self.device))
-        self.pending[key] = (guessed, weakref.ref(func) if func is not None else None, self._last_enqueued.pop(key, guessed))
-        self._seq[key] = self.blind_solves
-        self.blind_solves += 1
-
-    def learned(self, key, steps):
-        """A solve of `key` ran with a read-back: its count starts a new history."""
-        self.hist[key] = []
-        self.calm[key] = 0
-        self.fragile[key] = False
-        self.quiet[key] = 0
-        self._observe(key, int(steps))
-
-    def forget(self):
-        """Drop every step-count guess (the next solve of each kind runs with a read-back and learns its count anew)."""
-        for k in list(self.guess):
-            self.guess[k] = None
-            self.calm[k] = 0
-            self.hist[k] = []
-
-    def force_counts(self, counts):
-        """Tests: pretend every kind of solve (or those in the {key: n} mapping) has needed exactly n steps for a long
-        time -- the next blind solve enqueues n steps and no spare one."""
-        for k in list(self.guess):
-            n = counts.get(k) if isinstance(counts, dict) else counts
-            if n is None:
-                continue
-            self.guess[k] = int(n)
-            self.hist[k] = [int(n)] * self.CALM
-            self.calm[k] = self.CALM
-            self.fragile[k] = False
-            self.quiet[k] = self.QUIET
-
-    def step_verdicts(self):
-        """[(blind solve index, 'fwd' | 'bwd', missed)] for the records read so far (one iteration late): a caller that
-        logs losses or drives an LR schedule from them drops the iterations whose solves missed."""
-        return list(self.verdicts)
-
-    def settled(self):
-        """True once every kind of solve seen so far runs blind with exactly its last count (no spare step, no larger count
-        in the history window):
-        from then on a training step enqueues no launch that returns at once."""
-        return bool(self.guess) and all(g and not self._spare(k) and max(self.hist[k]) == self.hist[k][-1]
-                                        for k, g in self.guess.items())
-
-    def resolve(self):
-        """Wait for every outstanding record (a synchronisation point) and count the misses."""
-        for key in list(self.pending):
-            self.plan(key)
-        return self.misses
-
-
-class DeferredLoop:
-    """Training steps under deferred completion that never lose an update: a miss costs time, not training data.
-
-    `Deferred` alone SKIPS the optimizer step of an iteration one of whose solves missed.  Here the device flag is
-    STICKY -- nothing zeroes it behind the optimizer step, so once a solve has missed, that update and every later one
-    is skipped on the device -- and the host keeps each batch until its verdict is in.  `lag` iterations later (the copy
-    of the flag as the optimizer step saw it is long complete by then: no stall) the host reads the verdict; on a miss
-    it drains the queue, zeroes the flag, forgets the step-count guesses, and runs the voided batches again IN ORDER
-    with a read-back per solve, each under the random-generator state its first attempt started from.  The sequence
-    of committed updates is therefore exactly the synchronous run's (tests/test_gpu_deferred.py: parameters
-    bit-identical after a forced miss).  Under data parallelism the flag every rank reads is the all-reduced one
-    (`dp.GradientReducer.carry_flag`), so all ranks void and repeat the same batches together.
-
-        loop = integrate.DeferredLoop(deferred, opt, step_fn, reducer)     # step_fn(*batch) -> anything
-        for x, y in loader:
-            for result in loop.step(x, y):      # results of batches whose update is now known to be committed
-                log(result)
-        for result in loop.flush(): log(result)
-    """
-
-    def __init__(self, deferred: 'Deferred', opt, step_fn, reducer=None, lag: int = 1):
-        self.d, self.opt, self.step_fn, self.lag = deferred, opt, step_fn, max(0, int(lag))
-        opt.use_deferred(deferred, reducer)
-        opt.flags_to_reset = []            # sticky: only the host clears the flag, after it has seen the miss
-        self.queue: List[list] = []        # [batch, result, rng state, pinned flag copy, event]
-        self.retries = 0                   # batches run a second time
-        self.miss_events = 0
-        self.steps = 0
-        self._pool: List[tuple] = []       # (pinned float, event) pairs of settled entries, reused
-
-    def _rng(self):
-        return torch.cuda.get_rng_state(self.d.device), torch.get_rng_state()
-
-    def _set_rng(self, st):
-        torch.cuda.set_rng_state(st[0], self.d.device)
-        torch.set_rng_state(st[1])
-
-    def _run(self, batch):
-        with self.d:
-            return self.step_fn(*batch)
-
-    def _settle(self, keep: int):
-        """Pop committed entries until `keep` remain; on a miss repeat everything queued.  Returns committed results."""
-        out = []
-        while len(self.queue) > keep:
-            batch, result, rng, host, event = self.queue[0]
-            event.synchronize()
-            if float(host[0]) == 0.0:
-                self.queue.pop(0)
-                self._pool.append((host, event))
-                out.append(result)
-                continue
-            # a solve of this iteration (on some rank) missed: its update and every later one were skipped on the device
-            self.miss_events += 1
-            torch.cuda.synchronize(self.d.device)
-            self.d.resolve()
-            self.d.miss_flag.zero_()
-            self.d.forget()
-            voided, self.queue = self.queue, []
-            flag, self.opt.skip_flag = self.opt.skip_flag, None
-            armed, self.d.armed = self.d.armed, False
-            try:
-                for b, _, r, _, _ in voided:
-                    self._set_rng(r)      # the generator state the first attempt started from: after the last repeat
-                    out.append(self._run(b))   # it stands where the synchronous run's stands
-                    self.retries += 1
-            finally:
-                self.opt.skip_flag = flag
-                self.d.armed = armed
-        return out
-
-    def step(self, *batch):
-        done = self._settle(self.lag)
-        rng = self._rng()
-        result = self._run(batch)
-        host, event = self._pool.pop() if self._pool else (torch.zeros(1, dtype=torch.float32).pin_memory(), torch.cuda.Event())
-        src = self.opt.skip_flag if self.opt.skip_flag is not None else self.d.miss_flag
-        host.copy_(src, non_blocking=True)      # the flag as this iteration's optimizer step saw it
-        event.record(torch.cuda.current_stream(self.d.device))
-        self.queue.append([batch, result, rng, host, event])
-        self.steps += 1
-        return done
-
-    def flush(self):
-        return self._settle(0)
-
-
-_TOKENS = itertools.count(1)
-_TOKEN_OF: 'weakref.WeakKeyDictionary' = weakref.WeakKeyDictionary()
-
-
-def _func_token(func):
-    """A key for `func` that is never reused and never shared: id() can be handed to a new object after the old one
-    was collected (a new dynamics function would inherit a stale step-count guess), and an attribute on the module
-    would travel with `copy.deepcopy(model)` (an EMA / evaluation copy would share its original's pending record).
-    Tokens therefore live in a weak-keyed table beside the modules, not on them."""
-    try:
-        tok = _TOKEN_OF.get(func)
-        if tok is None:
-            tok = _TOKEN_OF[func] = next(_TOKENS)
-        return tok
-    except TypeError:          # not weak-referenceable / unhashable: fall back to identity
-        return id(func)
+def _solve_under_deferred(kind, wanted, func, state_shape, device, times, rtol, atol, method_id, options, solve):
+    """A solve under an optional `Deferred`: `solve(blind)` -> (..., stats), run blind (`blind` = Deferred.blind_args) with
+    the step count the open `Deferred` scope predicts for it, or with a read-back (`blind` = None) whose count the scope
+    learns.  Deferred completion only where a predicated commit point follows: training solves (`wanted`) over one
+    interval inside an armed `Deferred` scope; inference, sweeps and the drop-in API always return finished solves."""
+    d = Deferred.active if (wanted and method_id == _lib.METHOD_DOPRI5 and len(times) == 2 and _plain(options)) else None
+    if d is None or d.device != device:
+        return solve(None)
+    key = (kind, _func_token(func), tuple(state_shape), rtol, atol, tuple(times))
+    steps = d.plan(key, func)
+    if steps:
+        res = solve(d.blind_args(key, steps[1]))
+        st = res[-1]
+        st['nfe'] -= 6 * (steps[1] - steps[0])      # advance the counter by the guess; the record corrects it
+        st['accepted'] = steps[0]
+        d.launched(key, steps[0], func)
+    else:
+        res = solve(None)
+        d.learned(key, res[-1]['accepted'] + res[-1]['rejected'])
+    return res
 
 
 BACKPROP_LOG = 4096      # step sizes the forward solve can record for the non-adjoint backward (csrc: STEP_LIST_CAP)
@@ -720,23 +331,9 @@ class _HipOdeint(torch.autograd.Function):
         if not adjoint and wants_grad:
             options = dict(options or {})          # the backward replays the accepted steps: log their sizes
             options['record_dt'] = max(int(options.get('record_dt', 0) or 0), BACKPROP_LOG)
-        # deferred completion only where a predicated commit point follows: training solves (a gradient is wanted)
-        # inside an armed `Deferred` scope; inference, sweeps and the drop-in API always return finished solves
-        d = Deferred.active if (adjoint and wants_grad and method_id == _lib.METHOD_DOPRI5 and len(times) == 2
-                                and _plain(options)) else None
-        if d is not None and d.device != y0.device:
-            d = None
-        dkey = ('fwd', _func_token(func), tuple(y0.shape), rtol, atol, tuple(times)) if d is not None else None
-        steps = d.plan(dkey, func) if d is not None else None
-        if steps:
-            out, st = solve_forward(rec, list(params), y0, times, rtol, atol, method_id, options, blind=d.blind_args(dkey, steps[1]))
-            st['nfe'] -= 6 * (steps[1] - steps[0])      # advance the counter by the guess; the record corrects it
-            st['accepted'] = steps[0]
-            d.launched(dkey, steps[0], func)
-        else:
-            out, st = solve_forward(rec, list(params), y0, times, rtol, atol, method_id, options)
-            if d is not None:
-                d.learned(dkey, st['accepted'] + st['rejected'])
+        out, st = _solve_under_deferred(
+            'fwd', adjoint and wants_grad, func, y0.shape, y0.device, times, rtol, atol, method_id, options,
+            lambda blind: solve_forward(rec, list(params), y0, times, rtol, atol, method_id, options, blind=blind))
         func.nfe = getattr(func, 'nfe', 0) + st['nfe']          # model.py:340 convention
         func.last_forward_stats = st
         ctx.func, ctx.rec, ctx.times = func, rec, times
@@ -758,23 +355,10 @@ class _HipOdeint(torch.autograd.Function):
     def backward(ctx, grad_out):
         out, *params = ctx.saved_tensors
         if ctx.adjoint:
-            d = Deferred.active if (ctx.method_id == _lib.METHOD_DOPRI5 and len(ctx.times) == 2 and _plain(ctx.options)) else None
-            if d is not None and d.device != out.device:
-                d = None
-            dkey = ('bwd', _func_token(ctx.func), tuple(out.shape[1:]), ctx.rtol, ctx.atol, tuple(ctx.times)) if d is not None else None
-            steps = d.plan(dkey, ctx.func) if d is not None else None
-            if steps:
-                gy0, gp, _, st = solve_adjoint(ctx.rec, params, out, grad_out, ctx.times, ctx.rtol, ctx.atol,
-                                               ctx.method_id, ctx.options, blind=d.blind_args(dkey, steps[1]),
-                                               grad_last_only=ctx.last_only)
-                st['nfe'] -= 6 * (steps[1] - steps[0])
-                st['accepted'] = steps[0]
-                d.launched(dkey, steps[0], ctx.func)
-            else:
-                gy0, gp, _, st = solve_adjoint(ctx.rec, params, out, grad_out, ctx.times, ctx.rtol, ctx.atol,
-                                               ctx.method_id, ctx.options, grad_last_only=ctx.last_only)
-                if d is not None:
-                    d.learned(dkey, st['accepted'] + st['rejected'])
+            gy0, gp, _, st = _solve_under_deferred(
+                'bwd', True, ctx.func, out.shape[1:], out.device, ctx.times, ctx.rtol, ctx.atol, ctx.method_id, ctx.options,
+                lambda blind: solve_adjoint(ctx.rec, params, out, grad_out, ctx.times, ctx.rtol, ctx.atol, ctx.method_id,
+                                            ctx.options, blind=blind, grad_last_only=ctx.last_only))
             ctx.func.nfe = getattr(ctx.func, 'nfe', 0) + st['nfe']
             ctx.func.last_backward_stats = st
         else:
@@ -857,16 +441,9 @@ def odefunc_forward(func, t: float, y: torch.Tensor) -> torch.Tensor:
     lib = _lib.load()
     rec = Recognised(func)
     yc = y.detach().contiguous()
-    shape = _shape_struct(yc, rec)
-    pstruct, keep = _params_struct(rec.params, yc.device)
-    with torch.cuda.device(yc.device):
-        ws_bytes = lib.node_workspace_bytes(C.byref(shape), 0, 0, 2)
-        ws = _workspace(yc.device, ws_bytes)
-        out = torch.empty_like(yc)
-        rc = lib.node_odefunc_fwd(C.byref(shape), C.byref(pstruct), float(t), yc.data_ptr(), out.data_ptr(),
-                                  _aligned_ptr(ws), ws_bytes, torch.cuda.current_stream(yc.device).cuda_stream)
-    _lib.check(rc)
-    del keep
+    _, call = _marshal(rec, rec.params, yc, lib.node_workspace_bytes, 0, 0, 2)
+    out = torch.empty_like(yc)
+    call(lib.node_odefunc_fwd, float(t), yc.data_ptr(), out.data_ptr())
     return out
 
 
@@ -876,20 +453,12 @@ def odefunc_vjp(func, t: float, y: torch.Tensor, cot: torch.Tensor):
     lib = _lib.load()
     rec = Recognised(func)
     yc, cc = y.detach().contiguous(), cot.detach().contiguous()
-    shape = _shape_struct(yc, rec)
-    pstruct, keep = _params_struct(rec.params, yc.device)
-    with torch.cuda.device(yc.device):
-        ws_bytes = lib.node_workspace_bytes(C.byref(shape), 0, 1, 2)
-        ws = _workspace(yc.device, ws_bytes)
-        f = torch.empty_like(yc)
-        vy = torch.empty_like(yc)
-        vt = torch.empty(1, dtype=torch.float32, device=yc.device)
-        vp = torch.empty(lib.node_param_count(C.byref(shape)), dtype=torch.float32, device=yc.device)
-        rc = lib.node_odefunc_vjp(C.byref(shape), C.byref(pstruct), float(t), yc.data_ptr(), cc.data_ptr(),
-                                  f.data_ptr(), vy.data_ptr(), vt.data_ptr(), vp.data_ptr(),
-                                  _aligned_ptr(ws), ws_bytes, torch.cuda.current_stream(yc.device).cuda_stream)
-    _lib.check(rc)
-    del keep
+    shape, call = _marshal(rec, rec.params, yc, lib.node_workspace_bytes, 0, 1, 2)
+    f = torch.empty_like(yc)
+    vy = torch.empty_like(yc)
+    vt = torch.empty(1, dtype=torch.float32, device=yc.device)
+    vp = torch.empty(lib.node_param_count(C.byref(shape)), dtype=torch.float32, device=yc.device)
+    call(lib.node_odefunc_vjp, float(t), yc.data_ptr(), cc.data_ptr(), f.data_ptr(), vy.data_ptr(), vt.data_ptr(), vp.data_ptr())
     return f, vy, vt, vp
 
 

@@ -16,11 +16,11 @@ import torch
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from . import _lib
+from . import _lib, workspace
 from .odenet import FCClassifier, ResBlock, _Wrapped, _stem
 
-_FREE = {}        # (device, shape) -> workspaces whose backward has run: free for the next forward of that shape
-_SCRATCH = {}     # (device, stream, shape) -> the workspace of forwards that keep nothing
+_FREE = workspace.Carried()       # (device, shape) -> workspaces whose backward has run: free for the next forward of that shape
+_SCRATCH = workspace.Scratch()    # (device, stream, shape) -> the workspace of forwards that keep nothing
 
 
 def _block_params(blk):
@@ -62,10 +62,6 @@ def _struct_array(tensors):
     return arr
 
 
-def _aligned(ws):
-    return (ws.data_ptr() + 255) & ~255
-
-
 class _TrunkFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps, want_taps, keep, *params):
@@ -80,24 +76,19 @@ class _TrunkFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             nbytes = lib.node_trunk_workspace_bytes(C.byref(shape), 1 if keep else 0)
             if nbytes == 0:
-                raise _lib.NodeHipError(-3, lib.node_last_error().decode())
-            stream = torch.cuda.current_stream(dev).cuda_stream
+                _lib.unsupported()
             if keep:
-                # the workspace carries this forward's activations to its backward: one per forward in flight.  A training
-                # step runs forward then backward, so the previous step's buffer is free again; a second forward before the
-                # first one's backward (--batch-accumulation, two models) takes another.
+                # the workspace carries this forward's activations to its backward: one per forward in flight
+                # (--batch-accumulation, two models: workspace.Carried)
                 key = (dev.index,) + shape_args
-                free = _FREE.setdefault(key, [])
-                ws = free.pop() if free else torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+                ws = _FREE.take(key, dev, nbytes)
             else:
-                key = (dev.index, stream) + shape_args
-                ws = _SCRATCH.get(key)
-                if ws is None:
-                    ws = _SCRATCH[key] = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+                ws = _SCRATCH.take(dev, nbytes, *shape_args)
             out = torch.empty_like(x)
             taps = torch.empty((nblocks,) + tuple(x.shape), dtype=torch.float32, device=dev) if want_taps else None
             _lib.check(lib.node_trunk_fwd(C.byref(shape), _struct_array(ps), x.data_ptr(), out.data_ptr(),
-                                          taps.data_ptr() if want_taps else None, 1 if keep else 0, _aligned(ws), nbytes, stream))
+                                          taps.data_ptr() if want_taps else None, 1 if keep else 0, workspace.aligned_ptr(ws),
+                                          nbytes, torch.cuda.current_stream(dev).cuda_stream))
         if keep:
             ctx.shape_args, ctx.ws, ctx.nbytes, ctx.key = shape_args, ws, nbytes, key
             ctx.save_for_backward(*ps)
@@ -126,8 +117,9 @@ class _TrunkFn(torch.autograd.Function):
             grads = [torch.empty_like(p) for p in ps]
             dx = torch.empty_like(grad_out)
             _lib.check(lib.node_trunk_bwd(C.byref(shape), _struct_array(ps), grad_out.data_ptr(), _struct_array(grads),
-                                          dx.data_ptr(), _aligned(ws), ctx.nbytes, torch.cuda.current_stream(dev).cuda_stream))
-        _FREE[ctx.key].append(ws)     # free for the next forward of this shape (stream-ordered behind this backward)
+                                          dx.data_ptr(), workspace.aligned_ptr(ws), ctx.nbytes,
+                                          torch.cuda.current_stream(dev).cuda_stream))
+        _FREE.give(ctx.key, ws)       # free for the next forward of this shape (stream-ordered behind this backward)
         ctx.ws = None
         return (dx, None, None, None, *grads)
 

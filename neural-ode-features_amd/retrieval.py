@@ -14,20 +14,10 @@ from __future__ import annotations
 
 import torch
 
-from . import _lib
+from . import _lib, workspace
 
 MAX_DB = 16384
-_WS = {}
-
-
-def _workspace(device, nbytes):
-    """Caller-owned device scratch for the score chunk, one buffer per (device, stream)."""
-    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        _WS[key] = buf
-    return buf
+_WS = workspace.Scratch()      # the score chunk, one buffer per (device, stream)
 
 
 def _check_matrix(name, t):
@@ -111,8 +101,7 @@ def average_precision(queries, db, query_labels, db_labels, k=10):
     lib = _lib.load()
     nbytes = lib.node_retrieval_workspace_bytes(nq, nd, d)
     with torch.cuda.device(queries.device):
-        ws = _workspace(queries.device, nbytes)
-        ptr = (ws.data_ptr() + 255) & ~255
+        ptr = workspace.aligned_ptr(_WS.take(queries.device, nbytes))
         _lib.check(lib.node_retrieval_ap(nq, nd, d, queries.data_ptr(), db.data_ptr(), ql.data_ptr(), xl.data_ptr(), int(k),
                                          ap.data_ptr(), ap_k.data_ptr(), ptr, nbytes,
                                          torch.cuda.current_stream(queries.device).cuda_stream))

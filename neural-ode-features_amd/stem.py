@@ -13,9 +13,9 @@ import ctypes as C
 import torch
 from torch import nn
 
-from . import _lib
+from . import _lib, workspace
 
-_WS = {}
+_WS = workspace.Carried(keep=1)      # (device, shape) -> the workspace whose backward has run
 
 
 def _params_of(seq):
@@ -66,18 +66,15 @@ class _StemFn(torch.autograd.Function):
         with torch.cuda.device(dev):
             nbytes = lib.node_stem_workspace_bytes(C.byref(shape))
             if nbytes == 0:
-                raise _lib.NodeHipError(-3, lib.node_last_error().decode())
-            # the workspace carries the forward's activations to the backward: one per (device, shape) in flight.  A
-            # training step runs forward then backward, so the buffer of the previous step is free again; a second
-            # forward before the backward (two models, gradient accumulation over stems) takes a fresh buffer.
+                _lib.unsupported()
+            # the workspace carries the forward's activations to the backward: one per (device, shape) in flight (two
+            # models, gradient accumulation over stems: workspace.Carried)
             key = (dev.index, n, cin, h, w, filters)
-            ws = _WS.pop(key, None)
-            if ws is None or ws.numel() < nbytes + 256:
-                ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+            ws = _WS.take(key, dev, nbytes)
             h2 = ((h - 2 - 1) // 2 + 1 - 1) // 2 + 1
             w2 = ((w - 2 - 1) // 2 + 1 - 1) // 2 + 1
             out = torch.empty(n, filters, h2, w2, dtype=torch.float32, device=dev)
-            wsp = (ws.data_ptr() + 255) & ~255
+            wsp = workspace.aligned_ptr(ws)
             _lib.check(lib.node_stem_fwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), out.data_ptr(), wsp, nbytes,
                                          torch.cuda.current_stream(dev).cuda_stream))
         ctx.shape_args = (n, cin, h, w, filters, eps)
@@ -102,7 +99,7 @@ class _StemFn(torch.autograd.Function):
         ws = ctx.ws
         d_x = None
         with torch.cuda.device(dev):
-            wsp = (ws.data_ptr() + 255) & ~255
+            wsp = workspace.aligned_ptr(ws)
             stream = torch.cuda.current_stream(dev).cuda_stream
             if want_dx:
                 d_x = torch.empty_like(x)
@@ -112,7 +109,7 @@ class _StemFn(torch.autograd.Function):
             else:
                 _lib.check(lib.node_stem_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
                                              C.byref(_struct(grads)), wsp, ctx.nbytes, stream))
-        _WS[ctx.key] = ws            # free for the next forward of this shape (stream-ordered behind this backward)
+        _WS.give(ctx.key, ws)        # free for the next forward of this shape (stream-ordered behind this backward)
         ctx.ws = None
         if grads is None:
             grads = [None] * len(ps)
