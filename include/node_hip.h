@@ -613,6 +613,42 @@ typedef struct node_augment {
 int node_augment_batch(const node_augment* aug, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
                        uint64_t seed, uint32_t epoch, float* out, int64_t* out_labels, void* stream);
 
+/* The transfer evaluations' test transform -- evaluate.py:38-50, `Resize(side)`, `ToTensor`, `Normalize` on a PIL image -- as
+ * ONE launch per batch on a split that lives in device memory as uint8:
+ *   out_u8[b]     = Resize(data[index[b]])                                            uint8 [batch, c, out_h, out_w]
+ *   out_f32[b]    = Normalize(ToTensor(out_u8[b]))                                    fp32  [batch, c, out_h, out_w]
+ *   out_labels[b] = labels[index[b]]                                                  int64 [batch]
+ * Resize is PIL's `Image.resize((out_w, out_h), Image.BILINEAR)` on an 8-bit image, bit for bit.  Per axis, with `in` and
+ * `out` the sizes along it: scale = in / out (double), filterscale = support = max(scale, 1); output position xx has
+ * center = (xx + 0.5) scale, xmin = max(int(center - support + 0.5), 0), xmax = min(int(center + support + 0.5), in) and the
+ * weights w(x) = max(0, 1 - |(x - center + 0.5) / filterscale|) for x in [xmin, xmax), divided by their sum in double; the
+ * fixed-point coefficient of a weight is int(w 2^22 + 0.5), and an output byte is clip(((1 << 21) + sum coeff pixel) >> 22, 0,
+ * 255) in 32-bit integers.  The horizontal pass runs first, over every input row, and its result is rounded to bytes (they
+ * stay on chip); the vertical pass runs on those bytes.  A pass whose size does not change is skipped: in == out on both
+ * axes is the identity.  out_f32 is (byte / 255.f - mean[ch]) / std[ch] with `normalize`, byte / 255.f without: the
+ * expressions of node_augment_batch's test transform, so the two agree bit for bit on the same bytes.  Integer arithmetic
+ * and fixed orders throughout: every result is bit-reproducible.
+ * data: uint8 [n, c, h, w]; labels: int64 [n]; index: int64 [batch], all device memory.  out_f32 or out_u8 may be NULL, not
+ * both.  An index outside [0, n) reads nothing: a black image (normalised like any other) and the label -1.
+ * Supported: c in (1, 3), every size >= 1, h out_w <= 65536 (the bytes between the passes), every tensor below 2^31 elements
+ * and at most 2^24 coefficients per axis (NODE_ERR_UNSUPPORTED otherwise).  The coefficient tables are built on the host in
+ * double and kept per (device, in, out): the FIRST call of a size pair on a device allocates and copies them (and so cannot
+ * be captured into a graph); every later call only launches.  No workspace, no synchronisation.
+ *
+ * node_resize_table: host only, touches no device.  The table of one axis: xmin[out], count[out] (= xmax - xmin) and
+ * coeff[out * ksize], row xx holding its count coefficients then zeros.  Returns out * ksize, the capacity (int32 entries of
+ * coeff) it needs; xmin, count and coeff are written only when capacity is at least that (they may be NULL otherwise).  A
+ * negative return is a NODE_ERR_* code.  ksize = 2 ceil(support) + 1. */
+typedef struct node_resize {
+  int32_t n, c, h, w;        /* the split; c is 1 or 3                                                              */
+  int32_t out_h, out_w;
+  int32_t normalize;         /* != 0: out_f32 = (x - mean[ch]) / std[ch]                                            */
+  float mean[3], std[3];     /* normalize: the first c entries, std > 0                                             */
+} node_resize;
+int node_resize_batch(const node_resize* rs, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
+                      float* out_f32, uint8_t* out_u8, int64_t* out_labels, void* stream);
+int node_resize_table(int in, int out, int32_t* xmin, int32_t* count, int32_t* coeff, int capacity);
+
 /* The 4x4 stride-2 padding-1 convolution that turns the image into the ODE block's state -- the whole of the one-shot stem,
  * model.py:119-126 (`nn.Conv2d(in_ch, filters, 4, 2, 1)`), and the conv1 of the `ode` / `ode2` stems (model.py:185, 203):
  *     y = conv2d(x, weight, bias, stride 2, padding 1)

@@ -11,7 +11,7 @@ from .integrate import odeint, odeint_adjoint, odefunc_forward, odefunc_vjp  # n
 from .modules import ConcatConv2d, ODEBlock, ODEfunc, normalization  # noqa: F401
 from .odenet import FCClassifier, ODEDownsample, ODEDownsample2, ODENet, ResBlock, StackedODENet  # noqa: F401
 from . import attack, augment, dp, finetune, graphs, optim, retrieval  # noqa: F401
-from .augment import Augmenter, DeviceSplit  # noqa: F401
+from .augment import Augmenter, DeviceSplit, TransferTransform  # noqa: F401
 from .imgconv import ImageConv2d  # noqa: F401
 from .resnet import ResNet, ResidualTrunk, build_model  # noqa: F401
 from .optim import FusedAdam, FusedSGD  # noqa: F401

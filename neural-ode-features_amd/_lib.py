@@ -43,7 +43,7 @@ EXPORTS = [
     'node_flat_finish_step', 'node_flat_status_read',
     'node_retrieval_workspace_bytes', 'node_retrieval_ap', 'node_rank_ap',
     'node_svm_workspace_bytes', 'node_svm_fit', 'node_svm_cv_score',
-    'node_augment_batch',
+    'node_augment_batch', 'node_resize_batch', 'node_resize_table',
     'node_imgconv_workspace_bytes', 'node_imgconv_fwd', 'node_imgconv_bwd',
     'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd',
 ]
@@ -188,6 +188,11 @@ class NodeAugment(C.Structure):
                 ('flags', C.c_uint32), ('saturation', C.c_float), ('hue', C.c_float), ('mean', C.c_float * 3), ('std', C.c_float * 3)]
 
 
+class NodeResize(C.Structure):
+    _fields_ = [('n', C.c_int32), ('c', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('out_h', C.c_int32), ('out_w', C.c_int32),
+                ('normalize', C.c_int32), ('mean', C.c_float * 3), ('std', C.c_float * 3)]
+
+
 class NodeImgConvShape(C.Structure):
     _fields_ = [('n', C.c_int32), ('in_ch', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('filters', C.c_int32)]
 
@@ -209,6 +214,11 @@ class NodeHipError(RuntimeError):
     def __init__(self, code, message):
         self.code = code
         super().__init__('libnode_hip: %s (%d): %s' % (ERRORS.get(code, '?'), code, message))
+
+
+class NodeHipUnsupported(NodeHipError, NotImplementedError):
+    """NODE_ERR_UNSUPPORTED: a shape no kernel is built for.  A NodeHipError like every other code, and a NotImplementedError
+    like the shapes the Python layer refuses itself."""
 
 
 _lib = None
@@ -335,6 +345,10 @@ def load():
     lib.node_svm_cv_score.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, vp, vp, vp]
     lib.node_augment_batch.restype = i32
     lib.node_augment_batch.argtypes = [P(NodeAugment), vp, vp, vp, i32, C.c_uint64, C.c_uint32, vp, vp, vp]
+    lib.node_resize_batch.restype = i32
+    lib.node_resize_batch.argtypes = [P(NodeResize), vp, vp, vp, i32, vp, vp, vp, vp]
+    lib.node_resize_table.restype = i32
+    lib.node_resize_table.argtypes = [i32, i32, P(C.c_int32), P(C.c_int32), P(C.c_int32), i32]
     lib.node_imgconv_workspace_bytes.restype = sz
     lib.node_imgconv_workspace_bytes.argtypes = [P(NodeImgConvShape)]
     lib.node_imgconv_fwd.restype = i32
@@ -356,9 +370,9 @@ def load():
 
 def check(rc):
     if rc != 0:
-        raise NodeHipError(rc, load().node_last_error().decode('utf-8', 'replace'))
+        raise (NodeHipUnsupported if rc == NODE_ERR_UNSUPPORTED else NodeHipError)(rc, load().node_last_error().decode('utf-8', 'replace'))
 
 
 def unsupported():
     """A workspace-size query returned 0: the library refuses the geometry and has said why."""
-    raise NodeHipError(NODE_ERR_UNSUPPORTED, load().node_last_error().decode('utf-8', 'replace'))
+    raise NodeHipUnsupported(NODE_ERR_UNSUPPORTED, load().node_last_error().decode('utf-8', 'replace'))

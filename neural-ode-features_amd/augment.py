@@ -12,6 +12,13 @@ The random numbers are Philox4x32-10 keyed by `seed` and counted by (dataset ind
 depend on the batch it arrives in, its position there, the batch size or the rank, and a batch that is run a second time
 (`integrate.DeferredLoop` after a missed step count) sees the same pixels.  The jitter follows torchvision's tensor
 formulas in fp32, not PIL's 8-bit HSV path.  There is no CPU path.
+
+The transfer evaluations' test transform (evaluate.py:38-50 of the reference: `Resize(side)`, `ToTensor`, `Normalize` on a PIL
+image) is one launch per batch as well (csrc/kernels_resize.hip): PIL's 8-bit bilinear resample, bit for bit.
+
+    tt = TransferTransform(64, dataset='tiny-imagenet-200')        # a CIFAR-10 split for a net trained on 64-pixel images
+    images, target = tt.batch(split, index)                        # fp32 [B, C, 64, 64], normalised
+    pixels = tt.resized(split, index)                              # uint8 [B, C, 64, 64]: what PIL's resize returns
 """
 from __future__ import annotations
 
@@ -132,3 +139,75 @@ class Augmenter:
                                               int(epoch), images.data_ptr(), target.data_ptr(),
                                               torch.cuda.current_stream(split.device).cuda_stream))
         return images, target
+
+
+class TransferTransform:
+    """`Resize(size)`, `ToTensor` and -- with `dataset` (PREPROC) or `mean` / `std` -- `Normalize`, as the reference applies them
+    to another dataset's test images (evaluate.py:38-50).  `size` is the output side, or `(h, w)`; the resize is PIL's
+    `Image.resize((w, h), Image.BILINEAR)` on the 8-bit image, bit for bit, and a size the split already has is the identity.
+    (torchvision's `Resize(int)` scales the SHORTER side and keeps the aspect ratio: the same thing on the square images of
+    the reference's datasets, and only there.)"""
+
+    def __init__(self, size, dataset=None, mean=None, std=None):
+        if isinstance(size, (tuple, list)):
+            if len(size) != 2:
+                raise ValueError('size must be an integer or (h, w) (got %r)' % (size,))
+            h, w = size
+        else:
+            h = w = size
+        for v in (h, w):
+            if isinstance(v, bool) or not isinstance(v, int) or v < 1:
+                raise ValueError('size must be an integer >= 1 or a pair (h, w) of them (got %r)' % (size,))
+        self.size = (h, w)
+        if (mean is None) != (std is None):
+            raise ValueError('mean and std come together')
+        if mean is None and dataset is not None:
+            if dataset not in PREPROC:
+                raise ValueError('%r is not a known dataset (%s): pass mean= and std=' % (dataset, ', '.join(PREPROC)))
+            mean, std = PREPROC[dataset]
+        self.mean = tuple(float(m) for m in mean) if mean is not None else None
+        self.std = tuple(float(s) for s in std) if std is not None else None
+        if self.std is not None and (len(self.std) != len(self.mean) or len(self.std) not in (1, 3) or min(self.std) <= 0):
+            raise ValueError('mean and std must hold 1 or 3 entries each, std > 0')
+
+    def descriptor(self, split_shape):
+        """The node_resize record of this transform on a split of shape [N, C, H, W]."""
+        n, c, h, w = (int(v) for v in split_shape)
+        d = _lib.NodeResize(n, c, h, w, self.size[0], self.size[1], int(self.mean is not None))
+        if self.mean is not None:
+            if len(self.mean) != c:
+                raise ValueError('%d-channel statistics for %d-channel images' % (len(self.mean), c))
+            d.mean[:c], d.std[:c] = self.mean, self.std
+        return d
+
+    def _launch(self, split, index, want_f32):
+        if not isinstance(split, DeviceSplit):
+            raise TypeError('split must be a DeviceSplit')
+        if not torch.is_tensor(index) or index.dim() != 1 or index.dtype != torch.int64:
+            raise TypeError('index must be a 1-D int64 tensor')
+        if not index.is_cuda:
+            raise RuntimeError('augment has no CPU path: index must live on a HIP device (got %s)' % index.device)
+        if index.device != split.device:
+            raise RuntimeError('index must live on %s (got %s)' % (split.device, index.device))
+        desc = self.descriptor(split.x.shape)
+        index = index.contiguous()
+        b = index.shape[0]
+        images = torch.empty((b, split.x.shape[1]) + self.size, dtype=torch.float32 if want_f32 else torch.uint8, device=split.device)
+        target = torch.empty(b, dtype=torch.int64, device=split.device)
+        if b == 0:
+            return images, target
+        lib = _lib.load()
+        with torch.cuda.device(split.device):
+            _lib.check(lib.node_resize_batch(desc, split.x.data_ptr(), split.y.data_ptr(), index.data_ptr(), b,
+                                             images.data_ptr() if want_f32 else None, None if want_f32 else images.data_ptr(),
+                                             target.data_ptr(), torch.cuda.current_stream(split.device).cuda_stream))
+        return images, target
+
+    def batch(self, split, index):
+        """(images fp32 [B, C, h, w], target int64 [B]) of the dataset indices `index` (int64, on the split's device), enqueued
+        on the current stream: resized, / 255, normalised when the transform has statistics."""
+        return self._launch(split, index, True)
+
+    def resized(self, split, index):
+        """The resized 8-bit images alone, uint8 [B, C, h, w]: what `ToTensor` is applied to."""
+        return self._launch(split, index, False)[0]

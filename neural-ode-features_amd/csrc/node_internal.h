@@ -578,6 +578,26 @@ struct AugmentArgs {
 void launch_augment(const AugmentArgs& a, int c, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
                     float* out, int64_t* out_labels, hipStream_t s);
 
+// PIL's 8-bit bilinear resize + ToTensor + Normalize of a batch of dataset indices, one launch (kernels_resize.hip; checks
+// and the coefficient tables: resize_api.hip).  One axis's table in device memory; coeff == nullptr: the pass is skipped.
+constexpr int RESIZE_THREADS = 256;
+constexpr int RESIZE_BITS = 22;                    // PIL's PRECISION_BITS = 32 - 8 - 2
+constexpr int RESIZE_LDS_BYTES = 65536;            // h * out_w, the bytes between the two passes
+struct ResizeAxis {
+  const int32_t* xmin;
+  const int32_t* count;
+  const int32_t* coeff;      // [out, ksize]
+  int ksize;
+};
+struct ResizeArgs {
+  int n, h, w, oh, ow;
+  int normalize;
+  float mean[3], std[3];
+  ResizeAxis horiz, vert;
+};
+void launch_resize(const ResizeArgs& a, int c, const uint8_t* data, const int64_t* labels, const int64_t* index, int batch,
+                   float* out_f32, uint8_t* out_u8, int64_t* out_labels, hipStream_t s);
+
 // the image convolution 4x4 / stride 2 / padding 1 in front of the ODE block (kernels_imgconv.hip; checks: imgconv_api.hip)
 constexpr int IMG_FWD_FILTERS = 32;    // filters per workgroup of the forward (filters % 64 == 0)
 constexpr int IMG_SLAB = 256;          // output pixels (flattened over n, oh, ow) per partial of the weight gradient

@@ -22,6 +22,14 @@
              solver (finetune.py) -> finetune.csv with the reference's columns block, t1, cv_accuracy, plus tol, and the refit
              at the best C per slice in svms/svm_b{block}_t{t1}.npz (evaluate.py:364-413)
 
+Transfer (`-d/--data {cifar10, tiny-imagenet-200}`, evaluate.py:30, 38-51, 311-312, 368-371): `features RUN -d NAME --data-file F.pt`
+extracts the features of ANOTHER dataset's test images (`x_test` uint8 [N, C, H, W], `y_test` in F.pt) with the run's net:
+resized to the side the run was trained on (`train.SHAPES`) exactly as `transforms.Resize` does on a PIL image, and normalised
+with the RUN dataset's statistics -- always, whatever the run's `--augmentation` was -- in one HIP launch per chunk
+(`augment.TransferTransform`) -> features-NAME.npz; `retrieval -d NAME` and `finetune -d NAME` read that file and write
+retrieval-NAME.csv, finetune-NAME.csv and svms-NAME/.  (The reference writes the transfer SVMs over the run's own `svms/`;
+that quirk is not kept.)  NAME only names the files: the images are the file's.
+
 A run trained with `train --model resnet` (the baseline, resnet.py) takes `features` -- seven "time points": the stem's output and
 the outputs of the six blocks, `t1s = linspace(0, 1, 7)`, `tols = [0]` (evaluate.py:65-67) -- and `retrieval` and `finetune` on them; the
 modes that sweep the ODE block (`nfe`, `tradeoff`, `accuracy`) refuse it.
@@ -34,6 +42,8 @@ trained with `--augmentation` gets its test transform (augment.py), a run withou
     python -m neural_ode_features_amd.evaluate nfe runs_cifar10/odenet --limit 100
     python -m neural_ode_features_amd.evaluate retrieval runs_cifar10/odenet
     python -m neural_ode_features_amd.evaluate finetune runs_cifar10/odenet --aggregate
+    python -m neural_ode_features_amd.evaluate features runs_cifar10/odenet -d tiny-imagenet-200 --data-file tiny_val.pt
+    python -m neural_ode_features_amd.evaluate finetune runs_cifar10/odenet -d tiny-imagenet-200
 """
 from __future__ import annotations
 
@@ -45,6 +55,50 @@ import types
 
 import numpy as np
 import torch
+
+
+TRANSFER_DATA = ('cifar10', 'tiny-imagenet-200')          # evaluate.py:448, 451, 457
+TRANSFER_CHUNK = 1024                                     # images per launch of the transfer transform
+
+
+def result_name(name, data):
+    """`features.npz` -> `features-<data>.npz` with `-d <data>` (evaluate.py:30, 311-312, 368-370); the same for directories."""
+    if data is None:
+        return name
+    stem, ext = os.path.splitext(name)
+    return '%s-%s%s' % (stem, data, ext)
+
+
+def load_transfer_file(path, in_ch):
+    """(`x_test` uint8 [N, in_ch, H, W], `y_test` [N]) of a `--data-file`, or a SystemExit that says what is wrong with it."""
+    if not os.path.exists(path):
+        raise SystemExit('--data-file %s not found' % path)
+    blob = torch.load(path, map_location='cpu')
+    if not isinstance(blob, dict) or 'x_test' not in blob or 'y_test' not in blob:
+        raise SystemExit('--data-file %s must hold x_test (uint8 [N, C, H, W]) and y_test' % path)
+    x, y = blob['x_test'], blob['y_test']
+    if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 4:
+        raise SystemExit('--data-file %s: x_test must be a uint8 tensor [N, C, H, W] (the resize starts from the 8-bit pixels); it is %s'
+                         % (path, '%s %s' % (x.dtype, tuple(x.shape)) if torch.is_tensor(x) else type(x).__name__))
+    if x.shape[1] != in_ch:
+        raise SystemExit('--data-file %s holds %d-channel images, the run was trained on %d-channel images'
+                         % (path, x.shape[1], in_ch))
+    if not torch.is_tensor(y) or y.dim() != 1 or y.shape[0] != x.shape[0]:
+        raise SystemExit('--data-file %s: y_test must hold one label per image of x_test' % path)
+    return x, y
+
+
+def transfer_test_set(p, data_file, device):
+    """evaluate.py:38-51: the file's test images resized to the side the run was trained on and normalised with the run
+    dataset's statistics, on the device, in chunks -> (fp32 [N, C, side, side] on the device, labels on the host)."""
+    import neural_ode_features_amd as nof
+    from .train import SHAPES
+    in_ch, side, _ = SHAPES[p.dataset]
+    x, y = load_transfer_file(data_file, in_ch)
+    split = nof.DeviceSplit(x, y, device)
+    tt = nof.TransferTransform(side, dataset=p.dataset)
+    order = torch.arange(len(split), device=split.device)
+    return torch.cat([tt.batch(split, order[i:i + TRANSFER_CHUNK])[0] for i in range(0, len(split), TRANSFER_CHUNK)]), y.cpu()
 
 
 def load_run(run_dir, which='best'):
@@ -93,6 +147,9 @@ def _needs_odenet(p, mode):
 def features(args):
     """evaluate.py:24-94."""
     model, p, xte, yte = load_run(args.run)
+    data = getattr(args, 'data', None)
+    if data is not None:                              # evaluate.py:38-51: another dataset's test images through the run's net
+        xte, yte = transfer_test_set(p, args.data_file, args.device)
     if args.limit:
         xte, yte = xte[:args.limit], yte[:args.limit]
     model = model.to(args.device).eval()
@@ -111,7 +168,7 @@ def features(args):
                 model.odeblock.tol = tol
             f = [model(xte[i:i + p.batch_size].to(args.device)).cpu().numpy() for i in range(0, xte.shape[0], p.batch_size)]
             feats.append(np.concatenate(f, -2))       # concat along the batch dimension
-    out = os.path.join(args.run, 'features.npz')
+    out = os.path.join(args.run, result_name('features.npz', data))
     np.savez(out, features=np.stack(feats), y_true=yte.numpy(), tols=np.array(args.tol), t1s=np.array(args.t1))
     print('features', np.stack(feats).shape, '->', out)
     return out
@@ -236,10 +293,11 @@ def retrieval(args, k=10):
     bit-for-bit the reference's inputs; 'asym' ranks the database of the last time slice, 'sym' that of the query's own
     slice (for 'ode' stems, whose slices are 2T, the same indices); every image is a query, and the query itself stays in
     the database.  -> retrieval.csv with the reference's columns ap_asym, ap_sym, ap10_asym, ap10_sym, t1, plus tol: one
-    row per (tol, t1, query)."""
+    row per (tol, t1, query).  With `-d NAME`: features-NAME.npz -> retrieval-NAME.csv."""
     import pandas as pd
     from .retrieval import average_precision
-    path = os.path.join(args.run, 'features.npz')
+    data = getattr(args, 'data', None)
+    path = os.path.join(args.run, result_name('features.npz', data))
     if not os.path.exists(path):
         raise SystemExit('no pre-extracted features found: %s (run the `features` mode first)' % path)
     with np.load(path) as f:
@@ -255,7 +313,7 @@ def retrieval(args, k=10):
             frames.append(pd.DataFrame({'ap_asym': ap_asym.cpu().numpy(), 'ap_sym': ap_sym.cpu().numpy(),
                                         'ap10_asym': ap10_asym.cpu().numpy(), 'ap10_sym': ap10_sym.cpu().numpy(),
                                         't1': t1, 'tol': tol}))
-    out = os.path.join(args.run, 'retrieval.csv')
+    out = os.path.join(args.run, result_name('retrieval.csv', data))
     df = pd.concat(frames, ignore_index=True)
     df.to_csv(out, index=False)
     print(df.groupby(['tol', 't1']).mean())
@@ -293,15 +351,17 @@ def finetune(args):
     with `t1s` doubled; slices, `t1s` and `block` are zipped.  -> finetune.csv with the reference's columns block, t1,
     cv_accuracy, plus tol: one row per (tol, slice); the refit at the best C (the reference pickles the estimator) as `coef
     [K, D]`, `intercept [K]`, `C` and `classes` in svms/svm_b{block}_t{t1}.npz, with `_tol{tol}` before the suffix when the
-    features hold more than one tolerance."""
+    features hold more than one tolerance.  With `-d NAME`: features-NAME.npz -> finetune-NAME.csv and svms-NAME/ (the reference
+    writes these SVMs into the run's own `svms/`, over those of the run's dataset: not kept)."""
     import pandas as pd
-    path = os.path.join(args.run, 'features.npz')
+    data = getattr(args, 'data', None)
+    path = os.path.join(args.run, result_name('features.npz', data))
     if not os.path.exists(path):
         raise SystemExit('no pre-extracted features found: %s (run the `features` mode first)' % path)
     p = _run_params(args.run)
     with np.load(path) as f:
         feats, y_true, t1s, tols = f['features'], f['y_true'], f['t1s'], f['tols']
-    svm_dir = os.path.join(args.run, 'svms')
+    svm_dir = os.path.join(args.run, result_name('svms', data))
     os.makedirs(svm_dir, exist_ok=True)
     rows = []
     for ti, tol in enumerate(tols):
@@ -317,14 +377,14 @@ def finetune(args):
             name = 'svm_b%d_t%g%s.npz' % (b, t1, '_tol%g' % tol if len(tols) > 1 else '')
             np.savez(os.path.join(svm_dir, name), coef=search.coef, intercept=search.intercept, C=search.best_C,
                      classes=search.classes)
-    out = os.path.join(args.run, 'finetune.csv')
+    out = os.path.join(args.run, result_name('finetune.csv', data))
     df = pd.DataFrame(rows, columns=['block', 't1', 'cv_accuracy', 'tol'])
     df.to_csv(out, index=False)
     print(df)
     return out
 
 
-def main(argv=None):
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description='features / nfe / tradeoff / accuracy / retrieval / finetune evaluations of the reference on the HIP '
                                              'backend')
     ap.add_argument('mode', choices=('features', 'nfe', 'tradeoff', 'accuracy', 'retrieval', 'finetune'))
@@ -333,7 +393,23 @@ def main(argv=None):
     ap.add_argument('--tol', type=float, nargs='+', default=[1e-3, 1e-2, 1e-1, 1e0, 1e1, 1e2])      # evaluate.py:423
     ap.add_argument('--limit', type=int, default=0, help='only the first N test images')
     ap.add_argument('-a', '--aggregate', action='store_true', help='finetune: one slice, the mean of the features over t1')
+    ap.add_argument('-d', '--data', choices=TRANSFER_DATA, default=None,
+                    help='features / retrieval / finetune: the transfer variant -- features of --data-file through the run\'s net, '
+                         'in files named after it')
+    ap.add_argument('--data-file', default=None, help='features -d: a .pt with x_test (uint8 [N, C, H, W]) and y_test')
     args = ap.parse_args(argv)
+    if args.data is not None and args.mode not in ('features', 'retrieval', 'finetune'):
+        raise SystemExit('-d/--data is a switch of features, retrieval and finetune (evaluate.py:448-457), not of %s' % args.mode)
+    if args.data_file is not None and (args.data is None or args.mode != 'features'):
+        raise SystemExit('--data-file goes with `features -d/--data NAME`')
+    if args.mode == 'features' and args.data is not None and args.data_file is None:
+        raise SystemExit('features -d %s needs --data-file FILE.pt (x_test uint8 [N, C, H, W], y_test): datasets are files here'
+                         % args.data)
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     if args.mode == 'finetune':          # reads files only; the solver asks for the device when the first slice reaches it
         return finetune(args)
     if not torch.cuda.is_available():
