@@ -492,7 +492,9 @@ int node_stem_conv0_dgrad(const node_stem_shape* shape, const float* w0, const f
 /* Diagnostics (tests): ONE convolution of the stem's kernel family on NCHW fp32 tensors, through the same layout /
  * split / MFMA kernels node_stem_fwd and node_stem_bwd use.  what: 0 forward y = conv2d(x, w, stride, pad);
  * 1 data gradient dx = conv_transpose of dy (x_h, x_w: the input's spatial size); 2 weight gradient dw.
- * x: [n, cin, x_h, x_w]; w / dw: [cout, cin, k, k]; y / dy: [n, cout, y_h, y_w]; k in {1, 3}; cin, cout % 64 == 0. */
+ * x: [n, cin, x_h, x_w]; w / dw: [cout, cin, k, k]; y / dy: [n, cout, y_h, y_w]; cin, cout % 64 == 0.  Geometries:
+ * k = 3 with pad 1 and k = 1 with pad 0, stride 1 or 2 (the residual stem's); k = 4 with stride 2 and pad 1 (the
+ * down-sampling convolution of the `convolution` / `ode2` stems, node_downconv_* below; x_h, x_w >= 4) and no other k = 4. */
 typedef struct node_conv_geom {
   int32_t n, cin, cout, x_h, x_w, k, stride, pad;
 } node_conv_geom;
@@ -535,6 +537,76 @@ int node_trunk_fwd(const node_trunk_shape* shape, const node_trunk_block* blocks
                    int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
 int node_trunk_bwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* grad_out,
                    const node_trunk_block_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
+/* The hand-off between the two solves of the `ode2` stem -- model.py:199-223 (`ODEDownsample2`: `conv2(norm(x))`):
+ *     y = conv(relu(norm(x))),   norm = nn.GroupNorm(min(32, cin), cin),   conv = nn.Conv2d(cin, cout, 4, 2, 1) with bias
+ * on the stem's kernels: the GroupNorm + ReLU pass writes the exact bf16 triples the gather GEMM reads, the 16 taps of the
+ * 4x4 filter are one K loop on the bf16 matrix pipe at fp32 accuracy, the bias is added in its epilogue; the data gradient
+ * runs as four parity classes of four taps, the weight gradient one kernel row per workgroup.  NHWC inside the workspace.
+ * x, d_x: [n, cin, h, w]; y, grad_y: [n, cout, oh, ow] with oh = (h + 2 - 4) / 2 + 1 (likewise ow), NCHW fp32.
+ *   cin, cout: powers of two in [64, 4096]; any n >= 1; h, w >= 4 with h w pixels that fit the GroupNorm passes' LDS block
+ *   (2400 at cin <= 256); tensors under 2^31 elements.  Anything else: NODE_ERR_UNSUPPORTED with a message; the
+ *   workspace-size call returns 0 with the same message.
+ * keep_for_backward = 0: the forward alone (a smaller workspace).  With 1 the backward needs the workspace exactly as the
+ * forward left it.  node_downconv_bwd writes (does not accumulate) d_x (required) and, with grads given (NULL: the input
+ * gradient only -- no weight-gradient and no reduction launch), all four parameter gradients.  No floating-point atomics:
+ * every sum, the bias gradient's included, runs in a fixed order, so results are bit-reproducible run to run.  The calls
+ * never synchronise, allocate device memory or read back. */
+typedef struct node_downconv_shape {
+  int32_t n, cin, cout, h, w;
+  float eps;
+} node_downconv_shape;
+typedef struct node_downconv_params {    /* state_dict keys under `downsample.` of an `ode2` net */
+  const float* gn_w;     /* norm.0.weight [cin]               */
+  const float* gn_b;     /* norm.0.bias   [cin]               */
+  const float* conv_w;   /* conv2.weight  [cout, cin, 4, 4]   */
+  const float* conv_b;   /* conv2.bias    [cout]              */
+} node_downconv_params;
+typedef struct node_downconv_grads {     /* same order and shapes; device pointers, all required when given */
+  float* gn_w; float* gn_b; float* conv_w; float* conv_b;
+} node_downconv_grads;
+size_t node_downconv_workspace_bytes(const node_downconv_shape* shape, int keep_for_backward);
+int node_downconv_fwd(const node_downconv_shape* shape, const node_downconv_params* params, const float* x, float* y,
+                      int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_downconv_bwd(const node_downconv_shape* shape, const node_downconv_params* params, const float* grad_y,
+                      const node_downconv_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
+/* The `convolution` stem in front of the ODE block -- model.py:148-164 (`ConvDownsample`):
+ *     Conv2d(in_ch, 64, 3, 1) | GroupNorm(32, 64) + ReLU | Conv2d(64, 64, 4, 2, 1) | GroupNorm(32, 64) + ReLU |
+ *     Conv2d(64, filters, 4, 2, 1),  every convolution with bias
+ * on the same kernels as the residual stem and the hand-off above; NHWC inside the workspace, no layout transposes between
+ * the layers.  x: [n, in_ch, h, w]; out, grad_out: [n, filters, h2, w2] with h0 = h - 2, h1 = (h0 - 2) / 2 + 1,
+ * h2 = (h1 - 2) / 2 + 1 (likewise w), NCHW fp32.
+ *   in_ch <= 3; filters a power of two in [64, 4096]; h, w >= 10 and (h - 2)(w - 2) <= 2400 pixels (the GroupNorm passes hold
+ *   a (sample, 8 channels) block in LDS); tensors under 2^31 elements.  Anything else: NODE_ERR_UNSUPPORTED with a message;
+ *   the workspace-size call returns 0 with the same message.
+ * node_convstem_bwd needs the workspace exactly as node_convstem_fwd left it with keep_for_backward = 1.  It writes (does not
+ * accumulate) all ten parameter gradients; the image's gradient is not produced.  No floating-point atomics: every sum runs in
+ * a fixed order.  The calls never synchronise, allocate device memory or read back. */
+typedef struct node_convstem_shape {
+  int32_t n, in_ch, h, w, filters;
+  float eps;
+} node_convstem_shape;
+typedef struct node_convstem_params {    /* state_dict keys under `downsample.module.`, in state_dict order */
+  const float* c0_w;     /* 0.weight [64, in_ch, 3, 3]     */
+  const float* c0_b;     /* 0.bias   [64]                  */
+  const float* n1_w;     /* 1.weight [64]                  */
+  const float* n1_b;     /* 1.bias   [64]                  */
+  const float* c1_w;     /* 3.weight [64, 64, 4, 4]        */
+  const float* c1_b;     /* 3.bias   [64]                  */
+  const float* n2_w;     /* 4.weight [64]                  */
+  const float* n2_b;     /* 4.bias   [64]                  */
+  const float* c2_w;     /* 6.weight [filters, 64, 4, 4]   */
+  const float* c2_b;     /* 6.bias   [filters]             */
+} node_convstem_params;
+typedef struct node_convstem_grads {     /* same order and shapes; device pointers, all required */
+  float* c0_w; float* c0_b; float* n1_w; float* n1_b; float* c1_w; float* c1_b; float* n2_w; float* n2_b; float* c2_w; float* c2_b;
+} node_convstem_grads;
+size_t node_convstem_workspace_bytes(const node_convstem_shape* shape, int keep_for_backward);
+int node_convstem_fwd(const node_convstem_shape* shape, const node_convstem_params* params, const float* x, float* out,
+                      int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_params* params, const float* x, const float* grad_out,
+                      const node_convstem_grads* grads, void* ws, size_t ws_bytes, void* stream);
 
 /* Retrieval evaluation -- `evaluate.py retrieval` of the reference (evaluate.py:308-361).  For every query i, with scores
  * s_i[j] = q[i] . x[j] and relevance gt_i[j] = (q_labels[i] == x_labels[j]):

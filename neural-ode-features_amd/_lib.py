@@ -46,6 +46,8 @@ EXPORTS = [
     'node_augment_batch', 'node_resize_batch', 'node_resize_table',
     'node_imgconv_workspace_bytes', 'node_imgconv_fwd', 'node_imgconv_bwd',
     'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd',
+    'node_downconv_workspace_bytes', 'node_downconv_fwd', 'node_downconv_bwd',
+    'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd',
 ]
 
 
@@ -145,6 +147,29 @@ class NodeTrunkShape(C.Structure):
 
 class NodeTrunkBlock(C.Structure):          # node_trunk_block and node_trunk_block_grads share this layout
     _fields_ = [(k, C.c_void_p) for k in TRUNK_BLOCK_FIELDS]
+
+
+DOWNCONV_PARAM_FIELDS = ('gn_w', 'gn_b', 'conv_w', 'conv_b')
+
+
+class NodeDownConvShape(C.Structure):
+    _fields_ = [('n', C.c_int32), ('cin', C.c_int32), ('cout', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('eps', C.c_float)]
+
+
+class NodeDownConvParams(C.Structure):      # node_downconv_params and node_downconv_grads share this layout
+    _fields_ = [(k, C.c_void_p) for k in DOWNCONV_PARAM_FIELDS]
+
+
+CONVSTEM_PARAM_FIELDS = ('c0_w', 'c0_b', 'n1_w', 'n1_b', 'c1_w', 'c1_b', 'n2_w', 'n2_b', 'c2_w', 'c2_b')
+
+
+class NodeConvStemShape(C.Structure):
+    _fields_ = [('n', C.c_int32), ('in_ch', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('filters', C.c_int32),
+                ('eps', C.c_float)]
+
+
+class NodeConvStemParams(C.Structure):      # node_convstem_params and node_convstem_grads share this layout
+    _fields_ = [(k, C.c_void_p) for k in CONVSTEM_PARAM_FIELDS]
 
 
 class NodeConvGeom(C.Structure):
@@ -361,6 +386,18 @@ def load():
     lib.node_trunk_fwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, vp, vp, i32, vp, sz, vp]
     lib.node_trunk_bwd.restype = i32
     lib.node_trunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
+    lib.node_downconv_workspace_bytes.restype = sz
+    lib.node_downconv_workspace_bytes.argtypes = [P(NodeDownConvShape), i32]
+    lib.node_downconv_fwd.restype = i32
+    lib.node_downconv_fwd.argtypes = [P(NodeDownConvShape), P(NodeDownConvParams), vp, vp, i32, vp, sz, vp]
+    lib.node_downconv_bwd.restype = i32
+    lib.node_downconv_bwd.argtypes = [P(NodeDownConvShape), P(NodeDownConvParams), vp, P(NodeDownConvParams), vp, vp, sz, vp]
+    lib.node_convstem_workspace_bytes.restype = sz
+    lib.node_convstem_workspace_bytes.argtypes = [P(NodeConvStemShape), i32]
+    lib.node_convstem_fwd.restype = i32
+    lib.node_convstem_fwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, i32, vp, sz, vp]
+    lib.node_convstem_bwd.restype = i32
+    lib.node_convstem_bwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, sz, vp]
     ver = lib.node_abi_version()
     if ver != NODE_ABI_VERSION:
         raise RuntimeError('libnode_hip ABI %d != binding ABI %d' % (ver, NODE_ABI_VERSION))

@@ -1,0 +1,126 @@
+"""The `convolution` stem in front of the ODE block -- `ConvDownsample`, `/root/reference/model.py:148-164`:
+Conv2d(in_ch, 64, 3, 1) | GroupNorm + ReLU | Conv2d(64, 64, 4, 2, 1) | GroupNorm + ReLU | Conv2d(64, filters, 4, 2, 1) --
+forward and backward through the HIP library (`node_convstem_fwd / node_convstem_bwd`, csrc/convstem_api.hip on the kernels
+of csrc/kernels_stem.hip): ONE autograd node for the whole stem, NHWC inside, no MIOpen call, no layout transposes, no
+PyTorch reductions.  `ConvStem` IS the reference's `nn.Sequential` of seven children (same state_dict keys: `0.weight`,
+`1.weight`, `3.weight`, ...), so checkpoints load unchanged; CPU tensors, non-fp32 inputs, an input that requires a gradient
+(the fused backward produces parameter gradients only), a stream that is being captured and shapes the kernels refuse run the
+module sequence -- on a HIP device with the library missing, the fused path raises.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import torch
+from torch import nn
+
+from . import _lib, workspace
+
+_WS = workspace.Carried(keep=1)      # (device, shape) -> the workspace whose backward has run
+_FWD = workspace.Scratch()           # forwards that no backward follows (inference): nothing is carried
+
+
+def _params_of(seq):
+    """The ten tensors of the stem in node_convstem_params (= state_dict) order, or None if `seq` is not the reference's layout."""
+    try:
+        c0, n1, r1, c1, n2, r2, c2 = list(seq.children())
+    except ValueError:
+        return None
+    if not (isinstance(r1, nn.ReLU) and isinstance(r2, nn.ReLU)):
+        return None
+    for conv, geom in ((c0, ((3, 3), (1, 1), (0, 0))), (c1, ((4, 4), (2, 2), (1, 1))), (c2, ((4, 4), (2, 2), (1, 1)))):
+        if not isinstance(conv, nn.Conv2d) or conv.bias is None:
+            return None
+        if (conv.kernel_size, conv.stride, conv.padding) != geom or (conv.dilation, conv.groups, conv.padding_mode) != ((1, 1), 1, 'zeros'):
+            return None
+    for gn in (n1, n2):
+        if not (isinstance(gn, nn.GroupNorm) and gn.affine and gn.num_channels == 64 and gn.num_groups == 32 and gn.eps == n1.eps):
+            return None
+    if (c0.out_channels, c1.in_channels, c1.out_channels, c2.in_channels) != (64, 64, 64, 64):
+        return None
+    return [c0.weight, c0.bias, n1.weight, n1.bias, c1.weight, c1.bias, n2.weight, n2.bias, c2.weight, c2.bias]
+
+
+def _struct(tensors):
+    return _lib.NodeConvStemParams(*[t.data_ptr() for t in tensors])
+
+
+class _ConvStemFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, eps, keep, *params):
+        lib = _lib.load()
+        x = x.detach().contiguous()
+        ps = [p.detach().contiguous() for p in params]
+        n, cin, h, w = x.shape
+        filters = ps[-1].shape[0]
+        shape = _lib.NodeConvStemShape(n, cin, h, w, filters, eps)
+        dev = x.device
+        with torch.cuda.device(dev):
+            nbytes = lib.node_convstem_workspace_bytes(C.byref(shape), int(keep))
+            if nbytes == 0:
+                _lib.unsupported()
+            key = (dev.index, n, cin, h, w, filters)
+            # with a backward to come the workspace carries the activations to it: one per (device, shape) in flight
+            ws = _WS.take(key, dev, nbytes) if keep else _FWD.take(dev, nbytes, *key[1:])
+            h2, w2 = ((h - 2 - 2) // 2 + 1 - 2) // 2 + 1, ((w - 2 - 2) // 2 + 1 - 2) // 2 + 1
+            out = torch.empty(n, filters, h2, w2, dtype=torch.float32, device=dev)
+            _lib.check(lib.node_convstem_fwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), out.data_ptr(), int(keep),
+                                             workspace.aligned_ptr(ws), nbytes, torch.cuda.current_stream(dev).cuda_stream))
+        ctx.shape_args = (n, cin, h, w, filters, eps)
+        ctx.ws, ctx.nbytes, ctx.key = (ws if keep else None), nbytes, key
+        ctx.save_for_backward(x, *ps)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        lib = _lib.load()
+        x, *ps = ctx.saved_tensors
+        if ctx.ws is None:
+            raise RuntimeError('the fused stem keeps its activations in a workspace that the first backward releases: '
+                               'a second backward through the same forward (retain_graph=True) is not supported')
+        shape = _lib.NodeConvStemShape(*ctx.shape_args)
+        dev = x.device
+        grad_out = grad_out.contiguous()
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        grads = [torch.empty_like(p) for p in ps]
+        ws = ctx.ws
+        with torch.cuda.device(dev):
+            _lib.check(lib.node_convstem_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                             C.byref(_struct(grads)), workspace.aligned_ptr(ws), ctx.nbytes,
+                                             torch.cuda.current_stream(dev).cuda_stream))
+        _WS.give(ctx.key, ws)        # free for the next forward of this shape (stream-ordered behind this backward)
+        ctx.ws = None
+        return (None, None, None, *grads)
+
+
+def fusable(seq, x) -> bool:
+    """What the library's kernels take (node_convstem_fwd): fp32 on a HIP device, in_ch <= 3, filters a power of two >= 64,
+    images of up to 2400 pixels behind the first layer; an input that requires a gradient (saliency maps, attacks), a capturing
+    stream and anything else -- the 24-filter `minimal` stem, 64x64 inputs, filters = 192 -- run the module sequence."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1):
+        return False
+    if x.requires_grad and torch.is_grad_enabled():
+        return False
+    ps = _params_of(seq)
+    if ps is None or ps[0].shape[1] != x.shape[1]:
+        return False
+    if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in ps):
+        return False
+    if torch.cuda.is_current_stream_capturing():
+        return False
+    n, cin, h, w = x.shape
+    shape = _lib.NodeConvStemShape(n, cin, h, w, ps[-1].shape[0], seq[1].eps)
+    return _lib.load().node_convstem_workspace_bytes(C.byref(shape), 1) != 0      # (0: refused, with a message)
+
+
+class ConvStem(nn.Sequential):
+    """`nn.Sequential(Conv2d(in_ch, 64, 3, 1), GN, ReLU, Conv2d(64, 64, 4, 2, 1), GN, ReLU, Conv2d(64, out_ch, 4, 2, 1))` with
+    the reference's state_dict keys; on a HIP device its forward and backward are the library's (one autograd node)."""
+
+    def forward(self, x):
+        if not fusable(self, x):
+            return super().forward(x)
+        ps = _params_of(self)
+        keep = torch.is_grad_enabled() and any(p.requires_grad for p in ps)      # a backward may follow
+        return _ConvStemFn.apply(x, float(self[1].eps), keep, *ps)

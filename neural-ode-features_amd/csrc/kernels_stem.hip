@@ -354,7 +354,8 @@ __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
 //   accuracy.  Both operands are triples that already exist (the data gradient reads dy, the forward conv read `in`).
 //   The reduction runs over PIXELS, so an MFMA operand is eight consecutive pixels of one channel: the [pixel][channel]
 //   LDS images above, read with ds_read_b64_tr_b16 (a 4-row x 16-column block delivered column-major: the transpose is free).
-//   workgroup = (64 co x 64 ci tile, one kernel row ky = TG taps, one share of the pixels); wave w = the 32 x 32 block
+//   workgroup = (64 co x 64 ci tile, one kernel row ky = TG taps of a TG x TG filter, one share of the pixels; TG = 1, 3
+//   or 4: 1x1, 3x3 and the 4x4 stride-2 filters); wave w = the 32 x 32 block
 //   (w / 2, w % 2) for the TG taps; K chunk = 16 pixels = ONE MFMA K step: a dy image (6 KB) + TG gathered input images,
 //   through the ring above (D + 1 stages, D in flight).  Every workgroup writes its TG blocks of one slab; k_stem_reduce
 //   sums the slabs.
@@ -374,7 +375,7 @@ __device__ __forceinline__ void stem_wgrad_wave(const SWgradArgs& a, unsigned ch
   constexpr int H = W & 1;
   const int lane = threadIdx.x & 63;
   const int nct = a.Cin >> 6, npair = nct * (a.Cout >> 6);
-  const int ngrp = TG == 3 ? 3 : 1;
+  const int ngrp = TG;                               // kernel rows: one workgroup each
   int bb = blockIdx.x;
   const int pair = bb % npair; bb /= npair;
   const int ky = bb % ngrp;
@@ -400,7 +401,7 @@ __device__ __forceinline__ void stem_wgrad_wave(const SWgradArgs& a, unsigned ch
     const int pn = r / ohw, rem = r - pn * ohw;
     py = rem / a.OW;
     px = rem - py * a.OW;
-    irow = (pn * a.IH + py * a.stride - a.pad + (TG == 3 ? ky : 0)) * a.IW + px * a.stride - a.pad;
+    irow = (pn * a.IH + py * a.stride - a.pad + ky) * a.IW + px * a.stride - a.pad;
   }
   const bf16_t* dyb = a.dy3 + cot * 64 + sw;
   const bf16_t* dy2b = EX ? a.dy23 + cot * 64 + sw : nullptr;
@@ -410,7 +411,7 @@ __device__ __forceinline__ void stem_wgrad_wave(const SWgradArgs& a, unsigned ch
   size_t dyo, ino[TG];
   auto sources = [&]() {
     const bool valid = r < rend;
-    const int iy = py * a.stride - a.pad + (TG == 3 ? ky : 0), ix0 = px * a.stride - a.pad;
+    const int iy = py * a.stride - a.pad + ky, ix0 = px * a.stride - a.pad;
     const bool oky = valid && (unsigned)iy < (unsigned)a.IH;
     dyo = (size_t)(valid ? r : a.dy_zero_row) * a.Cout;
 #pragma unroll
@@ -503,10 +504,10 @@ __device__ __forceinline__ void stem_wgrad_wave(const SWgradArgs& a, unsigned ch
   for (; q + D < nchunk; ++q) step(q, std::true_type());
   for (; q < nchunk; ++q) step(q, std::false_type());
   const int li = lane & 31, hh = lane >> 5;
-  const int taps_total = TG == 3 ? 9 : 1;
+  const int taps_total = TG * TG;
 #pragma unroll
   for (int j = 0; j < NA; ++j) {
-    float* dst = j < TG ? a.slab + ((size_t)split * taps_total + (TG == 3 ? ky * 3 + j : 0)) * a.Cout * a.Cin
+    float* dst = j < TG ? a.slab + ((size_t)split * taps_total + ky * TG + j) * a.Cout * a.Cin
                         : a.slab2 + (size_t)split * a.Cout * a.Cin;
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
@@ -882,8 +883,10 @@ __global__ __launch_bounds__(256) void k_stem_gn_bwd(const SGnArgs a) {
 // ============================================================================
 // boundary layouts: NCHW fp32 <-> NHWC (fp32 and / or triples); 64 channels x 64 pixels per workgroup through LDS
 // ============================================================================
+// bpart (nullable) [N * ceil(HW / 64)][C]: per-channel sums of the workgroup's 64 pixels, taken in pixel order -- the partial sums of
+// a bias gradient when src is a convolution's output gradient (k_stem_reduce kind 3 adds them up)
 __global__ __launch_bounds__(256) void k_stem_from_nchw(const float* __restrict__ src, float* __restrict__ dst, bf16_t* __restrict__ dst3,
-                                                        size_t plane, int C, int HW) {
+                                                        size_t plane, int C, int HW, float* __restrict__ bpart) {
   __shared__ float tile[64][65];
   const int t = threadIdx.x;
   const int npb = (HW + 63) / 64, ncb = C / 64;
@@ -894,6 +897,12 @@ __global__ __launch_bounds__(256) void k_stem_from_nchw(const float* __restrict_
     tile[cc][pp] = p0 + pp < HW ? src[((size_t)n * C + c0 + cc) * HW + p0 + pp] : 0.f;
   }
   __syncthreads();
+  if (bpart != nullptr && t < 64) {       // (pixels past the image are zeros in the tile)
+    float s = 0.f;
+#pragma unroll 8
+    for (int pp = 0; pp < 64; ++pp) s += tile[t][pp];
+    bpart[((size_t)n * npb + pb) * C + c0 + t] = s;
+  }
   for (int idx = t; idx < 64 * 8; idx += 256) {
     const int pp = idx >> 3, q = idx & 7;
     if (p0 + pp >= HW) continue;
@@ -914,6 +923,27 @@ __global__ __launch_bounds__(256) void k_stem_from_nchw(const float* __restrict_
       *reinterpret_cast<u32x4*>(dst3 + o + 2 * plane) = ll;
     }
   }
+}
+
+// part[b][c] = sum of src[row][c] over the rows b * rows_per_blk .. + rows_per_blk - 1 of an fp32 NHWC tensor [rows][C]: the partial
+// sums of the bias gradient of a convolution whose output gradient a GroupNorm backward wrote (k_stem_reduce kind 3 adds them up).
+// thread = (channel t % 64 of the workgroup's 64, every fourth row); the four row classes meet in LDS in a fixed order.
+__global__ __launch_bounds__(256) void k_stem_colsum(const float* __restrict__ src, float* __restrict__ part, int rows, int C, int rows_per_blk) {
+  __shared__ float red[4][64];
+  const int t = threadIdx.x, cl = t & 63, sub = t >> 6;
+  const int nct = C >> 6;
+  const int blk = blockIdx.x / nct, c = (blockIdx.x - blk * nct) * 64 + cl;
+  const int r0 = blk * rows_per_blk, r1 = min(r0 + rows_per_blk, rows);
+  float s0 = 0.f, s1 = 0.f;
+  int r = r0 + sub;
+  for (; r + 4 < r1; r += 8) {
+    s0 += src[(size_t)r * C + c];
+    s1 += src[(size_t)(r + 4) * C + c];
+  }
+  if (r < r1) s0 += src[(size_t)r * C + c];
+  red[sub][cl] = s0 + s1;
+  __syncthreads();
+  if (sub == 0) part[(size_t)blk * C + c] = (red[0][cl] + red[1][cl]) + (red[2][cl] + red[3][cl]);
 }
 
 // fp32 -> triples, element for element (n % 8 == 0)
@@ -1024,10 +1054,10 @@ __global__ __launch_bounds__(256) void k_stem_reduce(const SReduceArgs a) {
       __syncthreads();
     }
   } else {
-    // kinds 1 (conv0: 64 x 32 words per slab, 450 slabs at cfg 2) and 2 (per-sample partials, 2 Co words): a workgroup sums 32 outputs, its
+    // kinds 1 (conv0: 64 x 32 words per slab, 450 slabs at cfg 2), 2 (per-sample partials, 2 Co words) and 3 (bias partials, Co words): a workgroup sums 32 outputs, its
     // eight 32-lane groups every eighth slab with eight loads in flight, the groups meet in LDS in a fixed order.  (One thread per output
     // and all slabs, four in flight: 113 dependent rounds at cfg 2 -- the 48 us this launch took.)
-    const size_t nout = j.kind == 1 ? (size_t)64 * 32 : (size_t)2 * j.Co;
+    const size_t nout = j.kind == 1 ? (size_t)64 * 32 : j.kind == 2 ? (size_t)2 * j.Co : (size_t)j.Co;
     const int o = t & 31, g = t >> 5;
     const size_t idx = (size_t)bx * 32 + o;
     if ((size_t)bx * 32 >= nout) return;
@@ -1083,8 +1113,9 @@ void launch_stem_conv(const SConvArgs& a, hipStream_t s) {
 
 void launch_stem_wgrad(const SWgradArgs& a, hipStream_t s) {
   const int taps = a.KH * a.KW;
-  const int grid = (a.Cin / 64) * (a.Cout / 64) * (taps == 9 ? 3 : 1) * a.nsplit;
-  const int nimg = 1 + (taps == 9 ? 3 : 1) + (a.dy23 ? 1 : 0);
+  const int krows = stem_wgrad_rows(taps);
+  const int grid = (a.Cin / 64) * (a.Cout / 64) * krows * a.nsplit;
+  const int nimg = 1 + krows + (a.dy23 ? 1 : 0);
 #define STEM_WG(T, EX, D)                                                                \
   {                                                                                       \
     static bool attr[MAX_DEVICES] = {};                                                   \
@@ -1095,10 +1126,12 @@ void launch_stem_wgrad(const SWgradArgs& a, hipStream_t s) {
   if (stem_ring()) {
     if (taps == 9 && a.dy23) STEM_WG(3, true, STEM_RING_D)
     else if (taps == 9) STEM_WG(3, false, STEM_RING_D)
+    else if (taps == 16) STEM_WG(4, false, STEM_RING_D)
     else STEM_WG(1, false, STEM_RING_D)
   } else {
     if (taps == 9 && a.dy23) STEM_WG(3, true, 1)
     else if (taps == 9) STEM_WG(3, false, 1)
+    else if (taps == 16) STEM_WG(4, false, 1)
     else STEM_WG(1, false, 1)
   }
 #undef STEM_WG
@@ -1164,8 +1197,12 @@ void launch_stem_prep(const SPrepArgs& a0, hipStream_t s) {
   a.blk0[8] = at;
   hipLaunchKernelGGL(k_stem_prep, dim3(at), dim3(256), 0, s, a);
 }
-void launch_stem_from_nchw(const float* src, float* dst_nhwc, bf16_t* dst3, size_t plane, int N, int C, int HW, hipStream_t s) {
-  hipLaunchKernelGGL(k_stem_from_nchw, dim3(N * (C / 64) * ((HW + 63) / 64)), dim3(256), 0, s, src, dst_nhwc, dst3, plane, C, HW);
+void launch_stem_from_nchw(const float* src, float* dst_nhwc, bf16_t* dst3, size_t plane, int N, int C, int HW, hipStream_t s, float* bpart) {
+  hipLaunchKernelGGL(k_stem_from_nchw, dim3(N * (C / 64) * ((HW + 63) / 64)), dim3(256), 0, s, src, dst_nhwc, dst3, plane, C, HW, bpart);
+}
+void launch_stem_colsum(const float* src, float* part, int rows, int C, int rows_per_blk, hipStream_t s) {
+  const int nblk = (rows + rows_per_blk - 1) / rows_per_blk;
+  hipLaunchKernelGGL(k_stem_colsum, dim3(nblk * (C / 64)), dim3(256), 0, s, src, part, rows, C, rows_per_blk);
 }
 void launch_stem_split(const float* src, bf16_t* dst3, size_t plane, size_t n, hipStream_t s) {
   hipLaunchKernelGGL(k_stem_split, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, s, src, dst3, plane, n / 8);
@@ -1179,7 +1216,7 @@ void launch_stem_reduce(const SReduceArgs& a0, hipStream_t s) {
   for (int i = 0; i < a.njobs; ++i) {
     const SReduceJob& j = a.job[i];
     a.blk0[i] = at;
-    at += (unsigned)(j.kind == 0 ? j.Co * j.taps : j.kind == 1 ? 64 : (2 * j.Co + 31) / 32);
+    at += (unsigned)(j.kind == 0 ? j.Co * j.taps : j.kind == 1 ? 64 : j.kind == 2 ? (2 * j.Co + 31) / 32 : (j.Co + 31) / 32);
   }
   a.blk0[a.njobs] = at;
   if (at == 0) return;

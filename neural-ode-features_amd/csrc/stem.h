@@ -72,6 +72,8 @@ struct SWgradArgs {
   int nsplit, rows_per_split;   // rows_per_split % 16 == 0
 };
 void launch_stem_wgrad(const SWgradArgs& a, hipStream_t s);
+// kernel rows of a square filter of `taps` taps (1x1, 3x3, 4x4): one workgroup and TG = rows accumulators per wave each
+inline int stem_wgrad_rows(int taps) { return taps == 16 ? 4 : taps == 9 ? 3 : 1; }
 
 // ----------------------------------------------------------------------------
 // first layer: nn.Conv2d(in_ch, 64, 3, 1) on the NCHW input, K = 9 in_ch <= 27 (fp32 MFMA)
@@ -123,13 +125,17 @@ struct SPrepArgs {
   unsigned blk0[9];                               // (filled by launch_stem_prep) first workgroup of job 0..5, of the conv0 job, of the zero job, and the end
 };
 void launch_stem_prep(const SPrepArgs& a, hipStream_t s);
-// NCHW fp32 -> NHWC fp32 (nullable) + triples (nullable); NHWC fp32 -> NCHW fp32
-void launch_stem_from_nchw(const float* src, float* dst_nhwc, bf16_t* dst3, size_t plane, int N, int C, int HW, hipStream_t s);
+// NCHW fp32 -> NHWC fp32 (nullable) + triples (nullable); NHWC fp32 -> NCHW fp32.  bpart (nullable) [N * ceil(HW / 64)][C]: the
+// per-channel sums of every 64-pixel block of src (a bias gradient's partial sums: reduce kind 3)
+void launch_stem_from_nchw(const float* src, float* dst_nhwc, bf16_t* dst3, size_t plane, int N, int C, int HW, hipStream_t s,
+                           float* bpart = nullptr);
 void launch_stem_to_nchw(const float* src_nhwc, float* dst, int N, int C, int HW, hipStream_t s);
 void launch_stem_split(const float* src, bf16_t* dst3, size_t plane, size_t n /* % 8 == 0 */, hipStream_t s);   // fp32 -> triples
+// per-channel sums of an fp32 NHWC tensor [rows][C] (C % 64 == 0) over blocks of rows_per_blk rows: part [ceil(rows / rows_per_blk)][C]
+void launch_stem_colsum(const float* src, float* part, int rows, int C, int rows_per_blk, hipStream_t s);
 // sums over split-K slabs / per-sample partials into the caller's gradient tensors
 //   kind 0: slab [ns][taps][Co][Ci] -> dW [Co][Ci][taps] (PyTorch layout); kind 1: conv0 slab [ns][64][32] -> dW0 [64][k0] + db [64];
-//   kind 2: GroupNorm partials [ns = N][2][C] -> dgamma [C], dbeta [C]
+//   kind 2: GroupNorm partials [ns = N][2][C] -> dgamma [C], dbeta [C]; kind 3: bias partials [ns][Co] -> db [Co]
 struct SReduceJob { const float* slab; float* out; float* out2; int kind, ns, Co, Ci, taps; };
 struct SReduceArgs { SReduceJob job[12]; int njobs; unsigned blk0[13]; };     // blk0: (filled by launch_stem_reduce) first workgroup of every job, and the end
 void launch_stem_reduce(const SReduceArgs& a, hipStream_t s);

@@ -449,8 +449,13 @@ int check_geom(const node_conv_geom* g) {
   if (!g) return fail(NODE_ERR_NULL, "geometry is NULL");
   if (g->n <= 0 || g->x_h <= 0 || g->x_w <= 0) return fail(NODE_ERR_SHAPE, "bad geometry");
   if (g->cin % 64 != 0 || g->cout % 64 != 0 || g->cin <= 0 || g->cout <= 0) return fail(NODE_ERR_UNSUPPORTED, "cin, cout must be multiples of 64");
+  if (g->k == 4) {     // the down-sampling convolution of the `convolution` / `ode2` stems: 4x4, stride 2, padding 1 and nothing else
+    if (g->stride != 2 || g->pad != 1) return fail(NODE_ERR_UNSUPPORTED, "4x4 filters run with stride 2 and padding 1 only (got stride %d, pad %d)", g->stride, g->pad);
+    if (g->x_h < 4 || g->x_w < 4) return fail(NODE_ERR_SHAPE, "a 4x4 stride-2 convolution takes images of 4x4 pixels and more");
+    return NODE_OK;
+  }
   if (!((g->k == 3 && g->pad == 1) || (g->k == 1 && g->pad == 0)) || (g->stride != 1 && g->stride != 2))
-    return fail(NODE_ERR_UNSUPPORTED, "3x3 pad 1 or 1x1 pad 0, stride 1 or 2");
+    return fail(NODE_ERR_UNSUPPORTED, "3x3 pad 1 or 1x1 pad 0, stride 1 or 2; 4x4 pad 1 stride 2");
   return NODE_OK;
 }
 }  // namespace

@@ -41,7 +41,7 @@ inline Wg take_wg(Bump& b, int rows, int Cout, int Cin, int taps, bool extra) {
   // workgroups = (64 x 64 tiles) x (kernel rows) x splits: aim at ~1.5 workgroups per CU, shares of >= 64 pixels,
   // and keep the slabs (written once, read once by k_stem_reduce) under ~16 MB
   Wg w;
-  const int pairs = (Cout / 64) * (Cin / 64) * (taps == 9 ? 3 : 1);
+  const int pairs = (Cout / 64) * (Cin / 64) * stem_wgrad_rows(taps);
   int ns = (384 + pairs - 1) / pairs;
   if (ns > rows / 64) ns = rows / 64;
   const size_t per = (size_t)(taps + (extra ? 1 : 0)) * Cout * Cin * sizeof(float);
@@ -99,7 +99,7 @@ inline SConvArgs conv_dgrad_args(const Trip& dy, const Filt& f, float* dx, int N
   int nc = 0, tiles = 0;
   for (int py = 0; py < 2; ++py)
     for (int px = 0; px < 2; ++px) {
-      int nt = 0, taps[9];
+      int nt = 0, taps[16];
       for (int ky = 0; ky < k; ++ky)
         for (int kx = 0; kx < k; ++kx)
           if (((py + pad - ky) & 1) == 0 && ((px + pad - kx) & 1) == 0) taps[nt++] = ky * k + kx;

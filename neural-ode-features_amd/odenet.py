@@ -54,7 +54,10 @@ def _stem(kind, in_ch, out_ch, norm):
     if kind in ('convolution', 'minimal'):   # model.py:129-164
         mid = 64 if kind == 'convolution' else 24
         make_norm = normalization(norm)
-        return nn.Sequential(
+        from .convstem import ConvStem
+        # 'convolution': forward / backward through the HIP library on a HIP device (convstem.py); 24 channels do not fit its tiles
+        body = ConvStem if kind == 'convolution' else nn.Sequential
+        return body(
             nn.Conv2d(in_ch, mid, 3, 1), make_norm(mid), nn.ReLU(inplace=True),
             nn.Conv2d(mid, mid, 4, 2, 1), make_norm(mid), nn.ReLU(inplace=True),
             nn.Conv2d(mid, out_ch, 4, 2, 1))
@@ -89,19 +92,39 @@ class ODEDownsample2(nn.Module):
         self.conv2 = nn.Conv2d(out_ch, out_ch, 4, 2, 1)
         self.apply_conv = False
 
+    # the hand-off `conv2(norm(x))` as one node of the HIP library (downconv.py) where its kernels take the shape; False: the
+    # GroupNorm + ReLU node and nn.Conv2d, as before that node existed (A/B runs, tests)
+    fused_handoff = True
+
     def _norm(self, x):
         from .head import gn_relu
         return gn_relu(x, self.norm[0])
 
+    def _handoff(self, x):
+        if not self.fused_handoff:
+            return self.conv2(self._norm(x))
+        from .downconv import gn_relu_conv
+        return gn_relu_conv(x, self.norm[0], self.conv2)
+
     def forward(self, x):
         x = self.odeblock(self.conv1(x))
         if x.dim() > 4:
+            if self.apply_conv and self.fused_handoff:
+                from .downconv import fusable, gn_relu_conv
+                flat = x.reshape(-1, *x.shape[2:])
+                if fusable(flat, self.norm[0], self.conv2):
+                    # GroupNorm is per sample, so the T time slices are one batch of T N samples: one call instead of T, and
+                    # every slice the bits of its own call (anything the kernels refuse keeps the per-slice modules below)
+                    y = gn_relu_conv(flat, self.norm[0], self.conv2)
+                    y = y.reshape(x.shape[0], x.shape[1], *y.shape[1:])
+                    return y, y[-1]
+            last = x[-1]
             x = torch.stack([self._norm(xi) for xi in x])
             if self.apply_conv:
                 x = torch.stack([self.conv2(xi) for xi in x])
                 return x, x[-1]
-            return x, self.conv2(x[-1])
-        return self.conv2(self._norm(x))
+            return x, (self._handoff(last) if self.fused_handoff else self.conv2(x[-1]))
+        return self._handoff(x)
 
 
 class _Wrapped(nn.Module):
