@@ -747,6 +747,27 @@ int node_imgconv_fwd(const node_imgconv_shape* shape, const float* x, const floa
 int node_imgconv_bwd(const node_imgconv_shape* shape, const float* x, const float* weight, const float* grad_y, float* d_weight,
                      float* d_bias, float* d_x, void* ws, size_t ws_bytes, void* stream);
 
+/* The hand-off between the two solves of the `ode` stem -- model.py:181-196, `ODEDownsample.maxpool` = nn.MaxPool2d(4, 2, 1) --
+ * and the plane means of the stem's trajectory in feature extraction (model.py:36, `fi.mean(-1).mean(-1)`).  fp32 NCHW.
+ *
+ * node_pool_fwd, ONE launch: x is a trajectory [t, n, c, h, w] (t = 1: a plain batch).
+ *   pooled [n, c, oh, ow]  the max-pool of the LAST slice, oh = (h - 2) / 2 + 1, ow = (w - 2) / 2 + 1 (integer division).
+ *                          ATen's semantics: padding counts as -inf; the window is scanned row-major with
+ *                          `val > max || isnan(val)`, so ties go to the first tap and a NaN wins and propagates.
+ *   argmax [n, c, oh, ow]  uint8 or NULL: the winning tap kh * 4 + kw (0..15) of input pixel (2 oh - 1 + kh, 2 ow - 1 + kw).
+ *   means  [t, n, c]       or NULL: sum over the plane / (h w) of every slice; one fixed summation order.
+ * node_pool_bwd, ONE launch: d_x [n, c, h, w] = the sum of grad_y [n, c, oh, ow] over the (at most 2 x 2) windows whose argmax
+ *   names the pixel, in ascending (oh, ow) order.  Every element of d_x is written exactly once (no zero-fill, nothing
+ *   accumulated, `t` is ignored); no atomics: bit-reproducible, and the bits of ATen's CPU backward.
+ * Any t, n, c >= 1 and 2 <= h, w <= 32768 with at most 2^40 elements; anything else is refused with NODE_ERR_UNSUPPORTED and a
+ * message.  Rows with w % 4 == 0 in 16-byte aligned tensors move as 16-byte accesses, everything else as scalars, with the
+ * same results.  The calls need no workspace and never synchronise, allocate or read back. */
+typedef struct node_pool_shape {
+  int32_t t, n, c, h, w;
+} node_pool_shape;
+int node_pool_fwd(const node_pool_shape* shape, const float* x, float* pooled, uint8_t* argmax, float* means, void* stream);
+int node_pool_bwd(const node_pool_shape* shape, const float* grad_y, const uint8_t* argmax, float* d_x, void* stream);
+
 /* Event-based per-kernel-class timing (off by default; adds two event records
  * per profiled launch).  begin() resets the counters; end() synchronises the
  * recorded events and fills `out`. */

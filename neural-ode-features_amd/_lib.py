@@ -48,6 +48,7 @@ EXPORTS = [
     'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd',
     'node_downconv_workspace_bytes', 'node_downconv_fwd', 'node_downconv_bwd',
     'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd',
+    'node_pool_fwd', 'node_pool_bwd',
 ]
 
 
@@ -220,6 +221,10 @@ class NodeResize(C.Structure):
 
 class NodeImgConvShape(C.Structure):
     _fields_ = [('n', C.c_int32), ('in_ch', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('filters', C.c_int32)]
+
+
+class NodePoolShape(C.Structure):
+    _fields_ = [('t', C.c_int32), ('n', C.c_int32), ('c', C.c_int32), ('h', C.c_int32), ('w', C.c_int32)]
 
 
 ATTACK_LINF, ATTACK_L2 = 0, 2
@@ -398,6 +403,10 @@ def load():
     lib.node_convstem_fwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, i32, vp, sz, vp]
     lib.node_convstem_bwd.restype = i32
     lib.node_convstem_bwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, sz, vp]
+    lib.node_pool_fwd.restype = i32
+    lib.node_pool_fwd.argtypes = [P(NodePoolShape), vp, vp, vp, vp, vp]
+    lib.node_pool_bwd.restype = i32
+    lib.node_pool_bwd.argtypes = [P(NodePoolShape), vp, vp, vp, vp]
     ver = lib.node_abi_version()
     if ver != NODE_ABI_VERSION:
         raise RuntimeError('libnode_hip ABI %d != binding ABI %d' % (ver, NODE_ABI_VERSION))

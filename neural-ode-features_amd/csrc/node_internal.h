@@ -608,4 +608,11 @@ void launch_imgconv_wgrad(const ImgConvArgs& a, int in_ch, const float* x, const
                           hipStream_t s);
 void launch_imgconv_dgrad(const ImgConvArgs& a, int in_ch, const float* w, const float* dy, float* dx, hipStream_t s);
 
+// the `ode` stem's hand-off: max-pool 4x4 / stride 2 / padding 1 of a trajectory's last slice and the plane means of every slice
+// (kernels_pool.hip; checks and the choice of the 16-byte path: pool_api.hip)
+constexpr int POOL_THREADS = 256;
+struct PoolArgs { int t, h, w, oh, ow; int64_t planes; };      // planes = n c
+void launch_pool_fwd(const PoolArgs& a, bool vec, const float* x, float* pooled, uint8_t* argmax, float* means, hipStream_t s);
+void launch_pool_bwd(const PoolArgs& a, bool vec, const float* gy, const uint8_t* argmax, float* dx, hipStream_t s);
+
 }  // namespace node

@@ -64,6 +64,12 @@ def _stem(kind, in_ch, out_ch, norm):
     raise NotImplementedError('downsample=%r' % (kind,))
 
 
+class StemTrajectory(tuple):
+    """(trajectory, continuation) of an ODE stem in feature-extraction mode; `means` [T, N, C]: the trajectory's plane means where
+    the stem has computed them along with the continuation (None: the caller pools)."""
+    means = None
+
+
 class ODEDownsample(nn.Module):
     """conv 4x4/2 -> ODE block -> max-pool 4x4/2 (model.py:181-196).  With `return_last_only` off the block
     returns its whole trajectory and this stem returns (trajectory, pooled last state)."""
@@ -72,13 +78,35 @@ class ODEDownsample(nn.Module):
         super().__init__()
         self.conv1 = ImageConv2d(in_ch, out_ch, 4, 2, 1)
         self.odeblock = ODEBlock(n_filters=out_ch, adjoint=adjoint, t1=t1, tol=tol, method=method, norm=norm)
-        self.maxpool = nn.MaxPool2d(4, 2, 1)
+        self.maxpool = nn.MaxPool2d(4, 2, 1)       # the geometry, and the path of everything the library's kernels do not take
 
-    def forward(self, x):
+    # the max-pool as one node of the HIP library (pool.py), and in feature extraction with a pool-only head the trajectory's
+    # plane means from the same launch; False: nn.MaxPool2d and the caller's means, as before that node existed (A/B runs, tests)
+    fused_pool = True
+
+    def _fused(self):
+        m = self.maxpool
+        return self.fused_pool and (m.kernel_size, m.stride, m.padding, m.dilation, m.ceil_mode, m.return_indices) == (4, 2, 1, 1, False, False)
+
+    def forward(self, x, with_means=False):
+        """with_means: the caller's head only pools (`ODENet.forward`), so a trajectory comes back with its plane means"""
         x = self.odeblock(self.conv1(x))
         if x.dim() > 4:
-            return x, self.maxpool(x[-1])
-        return self.maxpool(x)
+            if with_means and self._fused():
+                from .pool import fusable, trajectory_pool
+                if fusable(x) and not (torch.is_grad_enabled() and x.requires_grad):
+                    means, last = trajectory_pool(x)        # one launch: [T, N, C] and the second solve's initial state
+                    out = StemTrajectory((x, last))
+                    out.means = means
+                    return out
+            return StemTrajectory((x, self._pool(x[-1])))
+        return self._pool(x)
+
+    def _pool(self, x):
+        if not self._fused():
+            return self.maxpool(x)
+        from .pool import max_pool_4s2
+        return max_pool_4s2(x)
 
 
 class ODEDownsample2(nn.Module):
@@ -196,10 +224,18 @@ class ODENet(nn.Module):
 
     def forward(self, x):
         out = []
-        x = self.downsample(x)
+        if isinstance(self.downsample, ODEDownsample):
+            # a head that only pools (classification layer removed, model.py:53) takes the trajectory's plane means from the stem
+            head = getattr(self.classifier, 'module', None)
+            x = self.downsample(x, with_means=head is not None and isinstance(head[-1], nn.Sequential))
+        else:
+            x = self.downsample(x)
         if isinstance(x, (tuple, list)):     # an ODE stem in feature-extraction mode: (trajectory, continuation)
+            means = getattr(x, 'means', None)
             f, x = x
-            if isinstance(self.classifier.module[-1], nn.Sequential):   # classification layer removed: pool only
+            if means is not None:            # the stem's pool launch has produced them (pool.trajectory_pool)
+                f = means
+            elif isinstance(self.classifier.module[-1], nn.Sequential):   # classification layer removed: pool only
                 f = torch.stack([fi.mean(-1).mean(-1) for fi in f])
             else:
                 f = torch.stack([self.classifier(fi) for fi in f])
