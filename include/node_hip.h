@@ -607,6 +607,54 @@ int node_convstem_fwd(const node_convstem_shape* shape, const node_convstem_para
                       int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
 int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_params* params, const float* x, const float* grad_out,
                       const node_convstem_grads* grads, void* ws, size_t ws_bytes, void* stream);
+/* node_convstem_bwd plus the gradient of the image, d_x [n, in_ch, h, w] NCHW fp32 (required; written, not accumulated), with
+ * the contract of node_stem_bwd_dx: the first layer is the residual stem's Conv2d(in_ch, 64, 3, 1), so the same transposed
+ * first layer runs behind the data-gradient chain, in fp32 without atomics.  grads may be NULL (frozen parameters): then only
+ * the data-gradient chain runs -- no weight-gradient, partial-sum or reduction launch.  With grads given, the parameter
+ * gradients are node_convstem_bwd's bit for bit; d_x is the same bits with and without grads. */
+int node_convstem_bwd_dx(const node_convstem_shape* shape, const node_convstem_params* params, const float* x, const float* grad_out,
+                         const node_convstem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
+/* The `minimal` stem in front of the ODE block -- model.py:129-145 (`MinimalConvDownsample`):
+ *     Conv2d(in_ch, 24, 3, 1) | GroupNorm(24, 24) + ReLU | Conv2d(24, 24, 4, 2, 1) | GroupNorm(24, 24) + ReLU |
+ *     Conv2d(24, filters, 4, 2, 1),  every convolution with bias
+ * on kernels of its own (csrc/kernels_ministem.hip): register-tiled fp32 convolutions on NHWC tensors of channel pitch 24,
+ * GroupNorm with groups of ONE channel (statistics per (sample, channel) plane, one workgroup per sample).  Same geometry as
+ * the `convolution` stem: x: [n, in_ch, h, w]; out, grad_out: [n, filters, h2, w2], NCHW fp32.
+ *   in_ch <= 3; filters a power of two in [64, 4096]; h, w >= 10 (no upper limit on the image: no pass holds a plane in LDS);
+ *   tensors under 2^31 elements.  Anything else: NODE_ERR_UNSUPPORTED with a message; the workspace-size call returns 0 with
+ *   the same message.
+ * node_ministem_bwd needs the workspace exactly as node_ministem_fwd left it with keep_for_backward = 1.  It writes (does not
+ * accumulate) all ten parameter gradients (grads, nullable) and the image's gradient d_x [n, in_ch, h, w] (nullable).
+ * grads == NULL (frozen parameters): the data-gradient chain alone, no weight-gradient and no reduction launch; d_x == NULL:
+ * the transposed first layer is left out; both NULL: NODE_ERR_NULL.  The parameter gradients are the same bits with and
+ * without d_x, and d_x is the same bits with and without grads.  With one channel per group the gradients of 0.bias and
+ * 3.bias vanish in exact arithmetic; what is written is the rounding residue of the GroupNorm backward's own sums.  No
+ * floating-point atomics: every sum runs in a fixed order.  The calls never synchronise, allocate device memory or read back. */
+typedef struct node_ministem_shape {
+  int32_t n, in_ch, h, w, filters;
+  float eps;
+} node_ministem_shape;
+typedef struct node_ministem_params {    /* state_dict keys under `downsample.module.`, in state_dict order */
+  const float* c0_w;     /* 0.weight [24, in_ch, 3, 3]     */
+  const float* c0_b;     /* 0.bias   [24]                  */
+  const float* n1_w;     /* 1.weight [24]                  */
+  const float* n1_b;     /* 1.bias   [24]                  */
+  const float* c1_w;     /* 3.weight [24, 24, 4, 4]        */
+  const float* c1_b;     /* 3.bias   [24]                  */
+  const float* n2_w;     /* 4.weight [24]                  */
+  const float* n2_b;     /* 4.bias   [24]                  */
+  const float* c2_w;     /* 6.weight [filters, 24, 4, 4]   */
+  const float* c2_b;     /* 6.bias   [filters]             */
+} node_ministem_params;
+typedef struct node_ministem_grads {     /* same order and shapes; device pointers, all required when given */
+  float* c0_w; float* c0_b; float* n1_w; float* n1_b; float* c1_w; float* c1_b; float* n2_w; float* n2_b; float* c2_w; float* c2_b;
+} node_ministem_grads;
+size_t node_ministem_workspace_bytes(const node_ministem_shape* shape, int keep_for_backward);
+int node_ministem_fwd(const node_ministem_shape* shape, const node_ministem_params* params, const float* x, float* out,
+                      int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_ministem_bwd(const node_ministem_shape* shape, const node_ministem_params* params, const float* x, const float* grad_out,
+                      const node_ministem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
 
 /* Retrieval evaluation -- `evaluate.py retrieval` of the reference (evaluate.py:308-361).  For every query i, with scores
  * s_i[j] = q[i] . x[j] and relevance gt_i[j] = (q_labels[i] == x_labels[j]):

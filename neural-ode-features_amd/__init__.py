@@ -14,6 +14,7 @@ from . import attack, augment, dp, finetune, graphs, optim, retrieval  # noqa: F
 from .augment import Augmenter, DeviceSplit, TransferTransform  # noqa: F401
 from .imgconv import ImageConv2d  # noqa: F401
 from .convstem import ConvStem  # noqa: F401
+from .ministem import MinimalStem  # noqa: F401
 from .downconv import gn_relu_conv  # noqa: F401
 from .pool import max_pool_4s2, trajectory_pool  # noqa: F401
 from .resnet import ResNet, ResidualTrunk, build_model  # noqa: F401
@@ -21,4 +22,4 @@ from .optim import FusedAdam, FusedSGD  # noqa: F401
 from .head import cross_entropy, linear, linear_cross_entropy  # noqa: F401
 
 __all__ = ['odeint', 'odeint_adjoint', 'ODEBlock', 'ODEfunc', 'ConcatConv2d', 'ODENet', 'StackedODENet', 'ResNet', 'ResidualTrunk',
-           'ODEDownsample', 'ODEDownsample2', 'ConvStem', 'max_pool_4s2', 'trajectory_pool', 'dp']
+           'ODEDownsample', 'ODEDownsample2', 'ConvStem', 'MinimalStem', 'max_pool_4s2', 'trajectory_pool', 'dp']

@@ -47,7 +47,8 @@ EXPORTS = [
     'node_imgconv_workspace_bytes', 'node_imgconv_fwd', 'node_imgconv_bwd',
     'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd',
     'node_downconv_workspace_bytes', 'node_downconv_fwd', 'node_downconv_bwd',
-    'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd',
+    'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd', 'node_convstem_bwd_dx',
+    'node_ministem_workspace_bytes', 'node_ministem_fwd', 'node_ministem_bwd',
     'node_pool_fwd', 'node_pool_bwd',
 ]
 
@@ -170,6 +171,15 @@ class NodeConvStemShape(C.Structure):
 
 
 class NodeConvStemParams(C.Structure):      # node_convstem_params and node_convstem_grads share this layout
+    _fields_ = [(k, C.c_void_p) for k in CONVSTEM_PARAM_FIELDS]
+
+
+class NodeMiniStemShape(C.Structure):
+    _fields_ = [('n', C.c_int32), ('in_ch', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('filters', C.c_int32),
+                ('eps', C.c_float)]
+
+
+class NodeMiniStemParams(C.Structure):      # node_ministem_params and node_ministem_grads share this layout (and the field names)
     _fields_ = [(k, C.c_void_p) for k in CONVSTEM_PARAM_FIELDS]
 
 
@@ -403,6 +413,14 @@ def load():
     lib.node_convstem_fwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, i32, vp, sz, vp]
     lib.node_convstem_bwd.restype = i32
     lib.node_convstem_bwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, sz, vp]
+    lib.node_convstem_bwd_dx.restype = i32
+    lib.node_convstem_bwd_dx.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, vp, sz, vp]
+    lib.node_ministem_workspace_bytes.restype = sz
+    lib.node_ministem_workspace_bytes.argtypes = [P(NodeMiniStemShape), i32]
+    lib.node_ministem_fwd.restype = i32
+    lib.node_ministem_fwd.argtypes = [P(NodeMiniStemShape), P(NodeMiniStemParams), vp, vp, i32, vp, sz, vp]
+    lib.node_ministem_bwd.restype = i32
+    lib.node_ministem_bwd.argtypes = [P(NodeMiniStemShape), P(NodeMiniStemParams), vp, vp, P(NodeMiniStemParams), vp, vp, sz, vp]
     lib.node_pool_fwd.restype = i32
     lib.node_pool_fwd.argtypes = [P(NodePoolShape), vp, vp, vp, vp, vp]
     lib.node_pool_bwd.restype = i32

@@ -25,8 +25,10 @@ last without a graph) and `iterations` backwards (foolbox: twice the forwards). 
 each sample's gradient is its own; a batch shares dopri5's step sequence, as everywhere in this package (batch size 1
 reproduces the reference's per-image solves).
 
-fp32 images on a HIP device run the library's path: parameters frozen for the duration (the residual stem then runs its
-data-gradient chain alone, `ResidualStem.input_grad` / node_stem_bwd_dx), the fused loss, and two launches per iteration for
+fp32 images on a HIP device run the library's path: parameters frozen for the duration (the `residual`, `convolution` and
+`minimal` stems then run their data-gradient chains alone -- the `input_grad` switch of `ResidualStem`, `ConvStem` and
+`MinimalStem`: node_stem_bwd_dx, node_convstem_bwd_dx, node_ministem_bwd -- so an attack on a run of any of the three goes
+through the fused stem with no library convolution in it), the fused loss, and two launches per iteration for
 the attack's own arithmetic (node_attack_step, node_attack_judge; csrc/kernels_attack.hip).  Anything else -- CPU tensors,
 fp64, any callable model -- runs `bim_reference`, the same loop in plain torch, which is also what the tests compare against.
 
@@ -159,10 +161,13 @@ def bim_reference(model, images, labels, *, norm=INF, epsilon, stepsize, iterati
 
 @contextlib.contextmanager
 def _frozen(model, fused_stem):
-    """Parameters without gradients and the residual stems on their input-gradient path for the duration."""
+    """Parameters without gradients and the fused stems (residual, convolution, minimal) on their input-gradient path for the
+    duration."""
+    from .convstem import ConvStem
+    from .ministem import MinimalStem
     from .stem import ResidualStem
     params = [p for p in model.parameters() if p.requires_grad]
-    stems = [(m, m.input_grad) for m in model.modules() if isinstance(m, ResidualStem)]
+    stems = [(m, m.input_grad) for m in model.modules() if isinstance(m, (ResidualStem, ConvStem, MinimalStem))]
     for p in params:
         p.requires_grad_(False)
     for m, _ in stems:
@@ -234,8 +239,8 @@ def _bim_hip(model, images, labels, norm, epsilon, stepsize, iterations, return_
 def bim(model, images, labels, *, norm=INF, epsilon, stepsize, iterations=10, return_early=True, bounds=(0, 1),
         preprocessing=None, fused_stem=True):
     """The basic-iterative attack on a batch (module docstring).  `model`: normalised images -> logits; `images`: [n, C, H, W]
-    in pixel space `bounds`; `preprocessing`: (mean, std) per channel, or None.  `fused_stem=False` keeps a residual stem on
-    the module sequence (its default for inputs that require a gradient)."""
+    in pixel space `bounds`; `preprocessing`: (mean, std) per channel, or None.  `fused_stem=False` keeps a residual,
+    convolution or minimal stem on the module sequence (its default for inputs that require a gradient)."""
     norm = _norm_kind(norm)
     if images.dim() != 4 or labels.shape[0] != images.shape[0]:
         raise ValueError('images [n, C, H, W] and labels [n]')

@@ -6,7 +6,8 @@
 // backward (10 launches): NCHW -> triples of dy (+ the last bias gradient's partial sums) | per 4x4 convolution, last first:
 //                         weight gradient, data gradient, GN backward | the middle bias gradient's partial sums | conv0's weight
 //                         and bias gradient | ONE reduction launch: three slab sets, two GroupNorm partials, two bias partials
-// Parameter gradients only (the image's gradient is not produced).  Nothing is accumulated with atomics.
+// node_convstem_bwd_dx adds the transposed first layer behind dh0 (the image's gradient) and, with grads == NULL, runs the
+// data-gradient chain alone: no weight-gradient, partial-sum or reduction launch.  Nothing is accumulated with atomics.
 #include "host_common.h"
 #include "stem.h"
 #include "stem_plan.h"
@@ -178,12 +179,16 @@ int node_convstem_fwd(const node_convstem_shape* shape, const node_convstem_para
   return launch_ok("node_convstem_fwd");
 }
 
-int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_params* prm, const float* x, const float* grad_out,
-                      const node_convstem_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+}  // extern "C"
+
+namespace {
+// node_convstem_bwd (d_x NULL, gr required) and node_convstem_bwd_dx (d_x required, gr nullable: the data-gradient chain alone)
+int convstem_bwd(const node_convstem_shape* shape, const node_convstem_params* prm, const float* x, const float* grad_out,
+                 const node_convstem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream, const char* who) {
   int rc = check_convstem_shape(shape);
   if (rc != NODE_OK) return rc;
-  if (!prm || !x || !grad_out || !gr || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
-  if ((rc = check_ten(prm, "parameter")) != NODE_OK || (rc = check_ten(gr, "gradient")) != NODE_OK) return rc;
+  if (!prm || !x || !grad_out || (!gr && !d_x) || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if ((rc = check_ten(prm, "parameter")) != NODE_OK || (gr && (rc = check_ten(gr, "gradient")) != NODE_OK)) return rc;
   if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
   const ConvStemPlan p = make_convstem_plan(shape, true, ws);
   if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
@@ -191,11 +196,13 @@ int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_para
   const int N = p.N, F = p.F;
   const int HW0 = p.H0 * p.W0, HW1 = p.H1 * p.W1, HW2 = p.H2 * p.W2;
 
-  launch_stem_from_nchw(grad_out, nullptr, p.g2.p, p.g2.plane, N, F, HW2, st, p.bpart2);
+  launch_stem_from_nchw(grad_out, nullptr, p.g2.p, p.g2.plane, N, F, HW2, st, gr ? p.bpart2 : nullptr);
   if ((rc = launch_ok("stem_from_nchw")) != NODE_OK) return rc;
   // the last convolution (4x4 / 2, 64 -> F): reads a1
-  launch_stem_wgrad(wgrad_args(p.g2, nullptr, p.a1, p.w2, N, p.H1, p.W1, p.H2, p.W2, 64, F, 4, 2, 1), st);
-  if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  if (gr) {
+    launch_stem_wgrad(wgrad_args(p.g2, nullptr, p.a1, p.w2, N, p.H1, p.W1, p.H2, p.W2, 64, F, 4, 2, 1), st);
+    if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  }
   launch_stem_conv(conv_dgrad_args(p.g2, p.c2, p.da1, N, p.H2, p.W2, p.H1, p.W1, 4, 2, 1), st);
   if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
   {   // the gradient of h1 = the middle convolution's output: fp32 for its bias gradient, triples for the two GEMMs
@@ -204,11 +211,13 @@ int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_para
     launch_stem_gn_bwd(g, st);
     if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
   }
-  launch_stem_colsum(p.dh1, p.bpart1, p.R1, 64, BIAS_ROWS, st);
-  if ((rc = launch_ok("stem_colsum")) != NODE_OK) return rc;
   // the middle convolution (4x4 / 2, 64 -> 64): reads a0
-  launch_stem_wgrad(wgrad_args(p.dh1t, nullptr, p.a0, p.w1, N, p.H0, p.W0, p.H1, p.W1, 64, 64, 4, 2, 1), st);
-  if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  if (gr) {
+    launch_stem_colsum(p.dh1, p.bpart1, p.R1, 64, BIAS_ROWS, st);
+    if ((rc = launch_ok("stem_colsum")) != NODE_OK) return rc;
+    launch_stem_wgrad(wgrad_args(p.dh1t, nullptr, p.a0, p.w1, N, p.H0, p.W0, p.H1, p.W1, 64, 64, 4, 2, 1), st);
+    if ((rc = launch_ok("stem_wgrad")) != NODE_OK) return rc;
+  }
   launch_stem_conv(conv_dgrad_args(p.dh1t, p.c1, p.da0, N, p.H1, p.W1, p.H0, p.W0, 4, 2, 1), st);
   if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
   {
@@ -217,6 +226,11 @@ int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_para
     launch_stem_gn_bwd(g, st);
     if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
   }
+  if (d_x) {   // the transposed first layer (the residual stem's Conv2d(in_ch, 64, 3, 1)): dh0 -> the image
+    launch_stem_conv0_dgrad(p.dh0, prm->c0_w, d_x, N, p.Cin0, p.H, p.W, st);
+    if ((rc = launch_ok("stem_conv0_dgrad")) != NODE_OK) return rc;
+  }
+  if (!gr) return launch_ok(who);
   launch_stem_conv0_wgrad(x, p.dh0, p.w0.slab, N, p.Cin0, p.H, p.W, p.w0.nsplit, p.w0.rps, st);
   if ((rc = launch_ok("stem_conv0_wgrad")) != NODE_OK) return rc;
 
@@ -233,7 +247,28 @@ int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_para
   ra.njobs = nj;
   launch_stem_reduce(ra, st);
   if ((rc = launch_ok("stem_reduce")) != NODE_OK) return rc;
-  return launch_ok("node_convstem_bwd");
+  return launch_ok(who);
+}
+}  // namespace
+
+extern "C" {
+
+int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_params* prm, const float* x, const float* grad_out,
+                      const node_convstem_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+  if (!gr) {
+    const int rc = check_convstem_shape(shape);
+    return rc != NODE_OK ? rc : fail(NODE_ERR_NULL, "a required pointer is NULL");
+  }
+  return convstem_bwd(shape, prm, x, grad_out, gr, nullptr, ws, ws_bytes, stream, "node_convstem_bwd");
+}
+
+int node_convstem_bwd_dx(const node_convstem_shape* shape, const node_convstem_params* prm, const float* x, const float* grad_out,
+                         const node_convstem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream) {
+  if (!d_x) {
+    const int rc = check_convstem_shape(shape);
+    return rc != NODE_OK ? rc : fail(NODE_ERR_NULL, "a required pointer is NULL");
+  }
+  return convstem_bwd(shape, prm, x, grad_out, gr, d_x, ws, ws_bytes, stream, "node_convstem_bwd_dx");
 }
 
 }  // extern "C"

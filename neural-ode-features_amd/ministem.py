@@ -1,11 +1,11 @@
-"""The `convolution` stem in front of the ODE block -- `ConvDownsample`, `/root/reference/model.py:148-164`:
-Conv2d(in_ch, 64, 3, 1) | GroupNorm + ReLU | Conv2d(64, 64, 4, 2, 1) | GroupNorm + ReLU | Conv2d(64, filters, 4, 2, 1) --
-forward and backward through the HIP library (`node_convstem_fwd / node_convstem_bwd`, csrc/convstem_api.hip on the kernels
-of csrc/kernels_stem.hip): ONE autograd node for the whole stem, NHWC inside, no MIOpen call, no layout transposes, no
-PyTorch reductions.  `ConvStem` IS the reference's `nn.Sequential` of seven children (same state_dict keys: `0.weight`,
-`1.weight`, `3.weight`, ...), so checkpoints load unchanged; CPU tensors, non-fp32 inputs, an input that requires a gradient
-(unless `ConvStem.input_grad` is on: node_convstem_bwd_dx then returns the image's gradient too), a stream that is being captured
-and shapes the kernels refuse run the module sequence -- on a HIP device with the library missing, the fused path raises.
+"""The `minimal` stem in front of the ODE block -- `MinimalConvDownsample`, the reference's `model.py:129-145`:
+Conv2d(in_ch, 24, 3, 1) | GroupNorm(24, 24) + ReLU | Conv2d(24, 24, 4, 2, 1) | GroupNorm(24, 24) + ReLU |
+Conv2d(24, filters, 4, 2, 1) -- forward and backward through the HIP library (`node_ministem_fwd / node_ministem_bwd`,
+csrc/ministem_api.hip on the kernels of csrc/kernels_ministem.hip): ONE autograd node for the whole stem, NHWC inside, no
+MIOpen call, no layout transposes, no PyTorch reductions.  `MinimalStem` IS the reference's `nn.Sequential` of seven children
+(same state_dict keys: `0.weight`, `1.weight`, `3.weight`, ...), so checkpoints load unchanged; CPU tensors, non-fp32 inputs,
+`norm='batch'` children, a stream that is being captured, shapes the kernels refuse and -- with `input_grad` off -- an input
+that requires a gradient run the module sequence; on a HIP device with the library missing, the fused path raises.
 """
 from __future__ import annotations
 
@@ -16,12 +16,13 @@ from torch import nn
 
 from . import _lib, workspace
 
+MID = 24                             # the stem's middle channel count (model.py:133)
 _WS = workspace.Carried(keep=1)      # (device, shape) -> the workspace whose backward has run
 _FWD = workspace.Scratch()           # forwards that no backward follows (inference): nothing is carried
 
 
 def _params_of(seq):
-    """The ten tensors of the stem in node_convstem_params (= state_dict) order, or None if `seq` is not the reference's layout."""
+    """The ten tensors of the stem in node_ministem_params (= state_dict) order, or None if `seq` is not the reference's layout."""
     try:
         c0, n1, r1, c1, n2, r2, c2 = list(seq.children())
     except ValueError:
@@ -33,19 +34,19 @@ def _params_of(seq):
             return None
         if (conv.kernel_size, conv.stride, conv.padding) != geom or (conv.dilation, conv.groups, conv.padding_mode) != ((1, 1), 1, 'zeros'):
             return None
-    for gn in (n1, n2):
-        if not (isinstance(gn, nn.GroupNorm) and gn.affine and gn.num_channels == 64 and gn.num_groups == 32 and gn.eps == n1.eps):
+    for gn in (n1, n2):      # groups of one channel: GroupNorm(min(32, 24), 24)
+        if not (isinstance(gn, nn.GroupNorm) and gn.affine and gn.num_channels == MID and gn.num_groups == MID and gn.eps == n1.eps):
             return None
-    if (c0.out_channels, c1.in_channels, c1.out_channels, c2.in_channels) != (64, 64, 64, 64):
+    if (c0.out_channels, c1.in_channels, c1.out_channels, c2.in_channels) != (MID, MID, MID, MID):
         return None
     return [c0.weight, c0.bias, n1.weight, n1.bias, c1.weight, c1.bias, n2.weight, n2.bias, c2.weight, c2.bias]
 
 
 def _struct(tensors):
-    return _lib.NodeConvStemParams(*[t.data_ptr() for t in tensors])
+    return _lib.NodeMiniStemParams(*[t.data_ptr() for t in tensors])
 
 
-class _ConvStemFn(torch.autograd.Function):
+class _MiniStemFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, eps, keep, *params):
         lib = _lib.load()
@@ -53,10 +54,10 @@ class _ConvStemFn(torch.autograd.Function):
         ps = [p.detach().contiguous() for p in params]
         n, cin, h, w = x.shape
         filters = ps[-1].shape[0]
-        shape = _lib.NodeConvStemShape(n, cin, h, w, filters, eps)
+        shape = _lib.NodeMiniStemShape(n, cin, h, w, filters, eps)
         dev = x.device
         with torch.cuda.device(dev):
-            nbytes = lib.node_convstem_workspace_bytes(C.byref(shape), int(keep))
+            nbytes = lib.node_ministem_workspace_bytes(C.byref(shape), int(keep))
             if nbytes == 0:
                 _lib.unsupported()
             key = (dev.index, n, cin, h, w, filters)
@@ -64,7 +65,7 @@ class _ConvStemFn(torch.autograd.Function):
             ws = _WS.take(key, dev, nbytes) if keep else _FWD.take(dev, nbytes, *key[1:])
             h2, w2 = ((h - 2 - 2) // 2 + 1 - 2) // 2 + 1, ((w - 2 - 2) // 2 + 1 - 2) // 2 + 1
             out = torch.empty(n, filters, h2, w2, dtype=torch.float32, device=dev)
-            _lib.check(lib.node_convstem_fwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), out.data_ptr(), int(keep),
+            _lib.check(lib.node_ministem_fwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), out.data_ptr(), int(keep),
                                              workspace.aligned_ptr(ws), nbytes, torch.cuda.current_stream(dev).cuda_stream))
         ctx.shape_args = (n, cin, h, w, filters, eps)
         ctx.ws, ctx.nbytes, ctx.key = (ws if keep else None), nbytes, key
@@ -78,28 +79,22 @@ class _ConvStemFn(torch.autograd.Function):
         if ctx.ws is None:
             raise RuntimeError('the fused stem keeps its activations in a workspace that the first backward releases: '
                                'a second backward through the same forward (retain_graph=True) is not supported')
-        shape = _lib.NodeConvStemShape(*ctx.shape_args)
+        shape = _lib.NodeMiniStemShape(*ctx.shape_args)
         dev = x.device
         grad_out = grad_out.contiguous()
         if grad_out.dtype != torch.float32:
             grad_out = grad_out.float()
         # parameter gradients: all ten or none (an attack freezes the parameters: the data-gradient chain alone)
         want_params = any(ctx.needs_input_grad[3:])
-        want_dx = ctx.needs_input_grad[0]     # (only with ConvStem.input_grad: `fusable` sends any other such input elsewhere)
+        want_dx = ctx.needs_input_grad[0]     # (only with MinimalStem.input_grad: `fusable` sends any other such input elsewhere)
         grads = [torch.empty_like(p) for p in ps] if want_params or not want_dx else None
+        d_x = torch.empty_like(x) if want_dx else None
         ws = ctx.ws
-        d_x = None
         with torch.cuda.device(dev):
-            wsp = workspace.aligned_ptr(ws)
-            stream = torch.cuda.current_stream(dev).cuda_stream
-            if want_dx:
-                d_x = torch.empty_like(x)
-                _lib.check(lib.node_convstem_bwd_dx(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
-                                                    C.byref(_struct(grads)) if grads is not None else None, d_x.data_ptr(), wsp,
-                                                    ctx.nbytes, stream))
-            else:
-                _lib.check(lib.node_convstem_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
-                                                 C.byref(_struct(grads)), wsp, ctx.nbytes, stream))
+            _lib.check(lib.node_ministem_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                             C.byref(_struct(grads)) if grads is not None else None,
+                                             d_x.data_ptr() if d_x is not None else None, workspace.aligned_ptr(ws), ctx.nbytes,
+                                             torch.cuda.current_stream(dev).cuda_stream))
         _WS.give(ctx.key, ws)        # free for the next forward of this shape (stream-ordered behind this backward)
         ctx.ws = None
         if grads is None:
@@ -108,10 +103,9 @@ class _ConvStemFn(torch.autograd.Function):
 
 
 def fusable(seq, x, input_grad=False) -> bool:
-    """What the library's kernels take (node_convstem_fwd): fp32 on a HIP device, in_ch <= 3, filters a power of two >= 64,
-    images of up to 2400 pixels behind the first layer; an input that requires a gradient (saliency maps, attacks) only with
-    `input_grad` (node_convstem_bwd_dx); a capturing stream and anything else -- the 24-filter `minimal` stem (ministem.py has
-    its own kernels), 64x64 inputs, filters = 192 -- run the module sequence."""
+    """What the library's kernels take (node_ministem_fwd): fp32 on a HIP device, in_ch <= 3, filters a power of two in
+    [64, 4096], images of 10 x 10 pixels and more; an input that requires a gradient only with `input_grad`; a capturing stream
+    and anything else -- `norm='batch'` children, filters = 192 -- run the module sequence."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1):
         return False
     if x.requires_grad and torch.is_grad_enabled() and not input_grad:
@@ -124,17 +118,17 @@ def fusable(seq, x, input_grad=False) -> bool:
     if torch.cuda.is_current_stream_capturing():
         return False
     n, cin, h, w = x.shape
-    shape = _lib.NodeConvStemShape(n, cin, h, w, ps[-1].shape[0], seq[1].eps)
-    return _lib.load().node_convstem_workspace_bytes(C.byref(shape), 1) != 0      # (0: refused, with a message)
+    shape = _lib.NodeMiniStemShape(n, cin, h, w, ps[-1].shape[0], seq[1].eps)
+    return _lib.load().node_ministem_workspace_bytes(C.byref(shape), 1) != 0      # (0: refused, with a message)
 
 
-class ConvStem(nn.Sequential):
-    """`nn.Sequential(Conv2d(in_ch, 64, 3, 1), GN, ReLU, Conv2d(64, 64, 4, 2, 1), GN, ReLU, Conv2d(64, out_ch, 4, 2, 1))` with
+class MinimalStem(nn.Sequential):
+    """`nn.Sequential(Conv2d(in_ch, 24, 3, 1), GN, ReLU, Conv2d(24, 24, 4, 2, 1), GN, ReLU, Conv2d(24, out_ch, 4, 2, 1))` with
     the reference's state_dict keys; on a HIP device its forward and backward are the library's (one autograd node).
 
     `input_grad` (default False): with it on, an input that requires a gradient stays on the fused path and the backward
-    returns the image's gradient too (node_convstem_bwd_dx; with frozen parameters only the data-gradient chain runs).  Off, such
-    an input runs the module sequence, as it always has.  `nof.attack.bim` switches it on for the attack's duration."""
+    returns the image's gradient too (with frozen parameters only the data-gradient chain runs).  Off, such an input runs the
+    module sequence.  `nof.attack.bim` switches it on for the attack's duration."""
 
     input_grad = False
 
@@ -142,6 +136,7 @@ class ConvStem(nn.Sequential):
         if not fusable(self, x, self.input_grad):
             return super().forward(x)
         ps = _params_of(self)
-        grad = torch.is_grad_enabled()
-        keep = grad and (any(p.requires_grad for p in ps) or x.requires_grad)      # a backward may follow
-        return _ConvStemFn.apply(x, float(self[1].eps), keep, *ps)
+        want_x = x.requires_grad and torch.is_grad_enabled()
+        if not (torch.is_grad_enabled() and any(p.requires_grad for p in ps)):
+            return _MiniStemFn.apply(x, float(self[1].eps), want_x, *[p.detach() for p in ps])
+        return _MiniStemFn.apply(x, float(self[1].eps), True, *ps)

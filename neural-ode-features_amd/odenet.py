@@ -55,8 +55,10 @@ def _stem(kind, in_ch, out_ch, norm):
         mid = 64 if kind == 'convolution' else 24
         make_norm = normalization(norm)
         from .convstem import ConvStem
-        # 'convolution': forward / backward through the HIP library on a HIP device (convstem.py); 24 channels do not fit its tiles
-        body = ConvStem if kind == 'convolution' else nn.Sequential
+        from .ministem import MinimalStem
+        # forward / backward through the HIP library on a HIP device: the stem family's 64-column tiles (convstem.py) and, for
+        # the 24 channels that do not fit them, kernels of their own (ministem.py)
+        body = ConvStem if kind == 'convolution' else MinimalStem
         return body(
             nn.Conv2d(in_ch, mid, 3, 1), make_norm(mid), nn.ReLU(inplace=True),
             nn.Conv2d(mid, mid, 4, 2, 1), make_norm(mid), nn.ReLU(inplace=True),
