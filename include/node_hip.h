@@ -206,6 +206,18 @@ int node_conv3x3_w4(const node_shape* shape, const float* weight, int dgrad, con
  * x: n floats, out: 3 n floats (device); n a positive multiple of 8. */
 int node_w4_split3(const float* x, float* out, size_t n, void* stream);
 
+/* Diagnostics (tests): the launches that move a solve's tensors into and out of the state layout of the F(4x4,3x3) passes, and
+ * the border maps its set-up launch forms, on the caller's device buffers.  [n, c, 8, 8] or [n, c, 16, 16], c % 16 == 0.
+ *   node_w4s_layout       one tensor, NCHW -> state layout (to_nchw == 0) or back; src, dst: n c h w floats.
+ *   node_w4s_layout_jobs  njobs (1 or 2) tensors NCHW -> state layout in ONE launch; src[i], dst[i] as above (host arrays of
+ *                         device pointers); copies[2 i], copies[2 i + 1]: NCHW buffers that receive job i's source too, or NULL.
+ *   node_w4s_tmaps        tmap: [2][h w][c], the border-aware time-channel maps of two ConcatConv2d filters [c][c+1][3][3];
+ *                         tmap_s: [2][h w c], the same maps in the blocking the passes read, formed by the same launch. */
+int node_w4s_layout(const node_shape* shape, const float* src, float* dst, int to_nchw, void* stream);
+int node_w4s_layout_jobs(const node_shape* shape, int njobs, const float* const* src, float* const* dst, float* const* copies,
+                         void* stream);
+int node_w4s_tmaps(const node_shape* shape, const float* conv1_w, const float* conv2_w, float* tmap, float* tmap_s, void* stream);
+
 /* Diagnostics (tests; ABI 6): what the last node_solve_adjoint of the process did with the fp16-PAIR operand format of the
  * F(4x4,3x3) pipeline (csrc/wino4.h): out[0] = 1 when the solve used it, out[1] = steps the device controller REPEATED because a
  * cotangent left the range of its power-of-two scale (such a step is not a solver step: it appears in no statistic), out[2] = the

@@ -36,6 +36,7 @@ EXPORTS = [
     'node_head_fwd', 'node_head_bwd', 'node_gn_relu_fwd', 'node_gn_relu_bwd',
     'node_sgd_step', 'node_adam_step', 'node_profile_begin', 'node_profile_end',
     'node_conv3x3_w4_workspace_bytes', 'node_conv3x3_w4', 'node_w4_split3', 'node_w4_pair_stats',
+    'node_w4s_layout', 'node_w4s_layout_jobs', 'node_w4s_tmaps',
     'node_stem_workspace_bytes', 'node_stem_fwd', 'node_stem_bwd', 'node_stem_conv_workspace_bytes', 'node_stem_conv',
     'node_stem_bwd_dx', 'node_stem_conv0_dgrad_workspace_bytes', 'node_stem_conv0_dgrad', 'node_attack_step', 'node_attack_judge',
     'node_head_loss_scratch_bytes', 'node_head_loss_fwd', 'node_head_loss_bwd',
@@ -331,6 +332,12 @@ def load():
     lib.node_conv3x3_w4.argtypes = [P(NodeShape), vp, i32, vp, vp, vp, sz, vp]
     lib.node_w4_split3.restype = i32
     lib.node_w4_split3.argtypes = [vp, vp, sz, vp]
+    lib.node_w4s_layout.restype = i32
+    lib.node_w4s_layout.argtypes = [P(NodeShape), vp, vp, i32, vp]
+    lib.node_w4s_layout_jobs.restype = i32
+    lib.node_w4s_layout_jobs.argtypes = [P(NodeShape), i32, P(vp), P(vp), P(vp), vp]
+    lib.node_w4s_tmaps.restype = i32
+    lib.node_w4s_tmaps.argtypes = [P(NodeShape), vp, vp, vp, vp, vp]
     lib.node_stem_workspace_bytes.restype = sz
     lib.node_stem_workspace_bytes.argtypes = [P(NodeStemShape)]
     lib.node_stem_fwd.restype = i32

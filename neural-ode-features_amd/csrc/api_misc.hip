@@ -78,6 +78,57 @@ int node_conv3x3_w4(const node_shape* shape, const float* weight, int dgrad, con
   return NODE_OK;
 }
 
+// Diagnostics: the state-layout launches of an F(4x4,3x3) solve on the caller's tensors, and the border maps of its set-up launch.
+static int w4s_diag_geom(const node_shape* shape, int* Q) {
+  if (!shape) return fail(NODE_ERR_NULL, "shape is NULL");
+  const bool sq8 = shape->h == 8 && shape->w == 8, sq16 = shape->h == 16 && shape->w == 16;
+  if (!(sq8 || sq16) || shape->n < 1 || shape->c < 16 || shape->c % 16 != 0)
+    return fail(NODE_ERR_UNSUPPORTED, "the state layout of the F(4x4,3x3) passes takes 8x8 or 16x16 images, C %% 16 == 0");
+  *Q = sq16 ? 4 : 1;
+  return NODE_OK;
+}
+int node_w4s_layout(const node_shape* shape, const float* src, float* dst, int to_nchw, void* stream) {
+  int Q = 1;
+  TRY(w4s_diag_geom(shape, &Q));
+  if (!src || !dst) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if (to_nchw) launch_w4s_to_nchw(src, dst, shape->n, shape->c, Q, (hipStream_t)stream);
+  else launch_w4s_from_nchw(src, dst, shape->n, shape->c, Q, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+int node_w4s_layout_jobs(const node_shape* shape, int njobs, const float* const* src, float* const* dst, float* const* copies,
+                         void* stream) {
+  int Q = 1;
+  TRY(w4s_diag_geom(shape, &Q));
+  if (njobs < 1 || njobs > 2) return fail(NODE_ERR_ARG, "one or two jobs");
+  if (!src || !dst || !copies) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  W4sLayoutJobs lj;
+  memset(&lj, 0, sizeof(lj));
+  lj.njobs = njobs;
+  for (int i = 0; i < njobs; ++i) {
+    if (!src[i] || !dst[i]) return fail(NODE_ERR_NULL, "src / dst of a job is NULL");
+    lj.src[i] = src[i]; lj.dst[i] = dst[i]; lj.copy[i][0] = copies[2 * i]; lj.copy[i][1] = copies[2 * i + 1];
+  }
+  launch_w4s_from_nchw_jobs(lj, shape->n, shape->c, Q, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+int node_w4s_tmaps(const node_shape* shape, const float* conv1_w, const float* conv2_w, float* tmap, float* tmap_s, void* stream) {
+  int Q = 1;
+  TRY(w4s_diag_geom(shape, &Q));
+  if (!conv1_w || !conv2_w || !tmap || !tmap_s) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  Dims d;
+  memset(&d, 0, sizeof(d));
+  d.N = shape->n; d.C = shape->c; d.H = shape->h; d.W = shape->w; d.HW = shape->h * shape->w;     // (all launch_time_prep reads)
+  const size_t m = (size_t)d.HW * d.C;
+  launch_time_prep(d, conv1_w, conv2_w, tmap, tmap + m, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, tmap_s, tmap_s + m, Q);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
 int node_w4_pair_stats(int32_t* out4) {
   if (!out4) return fail(NODE_ERR_NULL, "out4 is NULL");
   for (int i = 0; i < 4; ++i) out4[i] = g_w4_pair_stats[i];

@@ -73,10 +73,26 @@ int node_solve_fwd(const node_shape* shape, const node_params* params, const flo
   S.choose_resident(method == NODE_METHOD_DOPRI5);
   if (method == NODE_METHOD_DOPRI5) S.take_norm_hook(opts);
   if (S.nr_fn != nullptr) S.resident = false;      // (global-norm mode: the host's hook sits between the launches of a step)
+  // dopri5: the record's reset and, for a deferred solve, its one target time ride in the preparation launch (SolveSetup) -- nothing
+  // between here and f0 reads either
+  const bool setup_rides = !S.resident && method == NODE_METHOD_DOPRI5;
+  bool y0_in_slot1 = false;      // a deferred solve's y_out[1] <- y0 was done by the state's layout launch
   if (!S.resident) {      // (the resident solve packs its filters, forms its border maps and copies y0 inside its one launch)
-    TRY(S.prepare());
-    S.to_state(y0, S.p.Y);
-    HIP_TRY(hipMemcpyAsync(y_out, y0, numel * sizeof(float), hipMemcpyDeviceToDevice, S.st));
+    SolveSetup su;
+    memset(&su, 0, sizeof(su));
+    su.ctrl = S.p.ctrl; su.set_ctrl = 1; su.t = ts[0]; su.dt = forced ? opts->forced_dt[0] : 0.0;
+    if (ctl.blind) { su.targets = S.p.targets; su.target = ts[1]; }
+    TRY(S.prepare(setup_rides ? &su : nullptr));
+    if (S.w4) {     // y0 -> the state, the trajectory's first slot and (deferred) the output slot a missed solve leaves alone: one launch
+      W4sLayoutJobs lj;
+      memset(&lj, 0, sizeof(lj));
+      lj.src[0] = y0; lj.dst[0] = S.p.Y; lj.copy[0][0] = y_out; lj.njobs = 1;
+      if (method == NODE_METHOD_DOPRI5 && ctl.blind) { lj.copy[0][1] = y_out + numel; y0_in_slot1 = true; }
+      launch_w4s_from_nchw_jobs(lj, S.d.N, S.d.C, S.d.w4q, S.st);
+    } else {
+      S.to_state(y0, S.p.Y);
+      HIP_TRY(hipMemcpyAsync(y_out, y0, numel * sizeof(float), hipMemcpyDeviceToDevice, S.st));
+    }
   }
 
   if (method == NODE_METHOD_RK4) {
@@ -105,10 +121,10 @@ int node_solve_fwd(const node_shape* shape, const node_params* params, const flo
   if (inline_targets) {
     if (blind) HIP_TRY(hipMemcpyAsync(y_out + numel, y0, numel * sizeof(float), hipMemcpyDeviceToDevice, S.st));
   } else if (blind) {
-    launch_set_target(S.p.targets, ts[1], S.st);
+    if (!setup_rides) launch_set_target(S.p.targets, ts[1], S.st);
     // a MISSED blind solve never emits its output: leave y0 there, not uninitialised memory (the caller's loss of
     // such a step is then a finite number of a step whose update is skipped anyway)
-    HIP_TRY(hipMemcpyAsync(y_out + numel, y0, numel * sizeof(float), hipMemcpyDeviceToDevice, S.st));
+    if (!y0_in_slot1) HIP_TRY(hipMemcpyAsync(y_out + numel, y0, numel * sizeof(float), hipMemcpyDeviceToDevice, S.st));
   } else {
     TRY(S.upload(S.p.targets, ts.data() + 1, n_t - 1, hs->lists));
   }
@@ -142,13 +158,15 @@ int node_solve_fwd(const node_shape* shape, const node_params* params, const flo
     }
   }
   if (!S.resident) {
-    launch_set_ctrl(S.p.ctrl, ts[0], forced ? opts->forced_dt[0] : 0.0, 1, S.st);
+    if (!setup_rides) launch_set_ctrl(S.p.ctrl, ts[0], forced ? opts->forced_dt[0] : 0.0, 1, S.st);   // (a resident solve that fell back)
     TRY(S.eval_sys(0, nullptr, 0, SC_ABS, S.et_stage(0.0), false));  // f0 (FSAL seed)
     if (!forced) TRY(S.initial_step());
   }
   if (blind) {
-    for (int i = 0; i < blind; ++i) TRY(S.enqueue_step(io));
-    launch_export_record(S.p.ctrl, opts->record, opts->miss_flag, blind, S.st);
+    for (int i = 0; i < blind; ++i) {
+      if (i == blind - 1) { io.rec = opts->record; io.miss_flag = opts->miss_flag; io.expect_steps = blind; }   // (the record rides in the last commit)
+      TRY(S.enqueue_step(io));
+    }
     stt.status = NODE_PENDING;
     stt.accepted = blind; stt.rejected = 0;            // predicted: true iff the record says no miss
     stt.nfe = S.nfe + 6 * blind;
@@ -206,16 +224,35 @@ int node_solve_adjoint(const node_shape* shape, const node_params* params, const
   S.choose_w4(method == NODE_METHOD_DOPRI5);   // (a replay of recorded steps runs the numerics of the solve it replays)
   S.w4_f16_aug = method == NODE_METHOD_DOPRI5;
   if (method == NODE_METHOD_DOPRI5) S.take_norm_hook(opts);
-  TRY(S.prepare());
+  {
+    // carried by the preparation launch (SolveSetup): the record's reset -- which also zeroes the scalar segment (adj_time = 0) --,
+    // adj_params = 0, and for dopri5 the FIRST interval's start and (deferred) target: nothing in front of that interval's first
+    // evaluation reads any of them.  Later intervals of a time grid keep their setters.
+    SolveSetup su;
+    memset(&su, 0, sizeof(su));
+    su.ctrl = S.p.ctrl; su.set_ctrl = 1; su.t = 0.0; su.dt = 0.0;
+    su.zero = S.p.TH; su.zero_n = S.d.P;
+    if (method != NODE_METHOD_RK4) {
+      const bool dec = t_pts[n_t - 2] < t_pts[n_t - 1];
+      su.set_interval = 1; su.iv_t = (double)(dec ? -t_pts[n_t - 1] : t_pts[n_t - 1]); su.iv_dt = forced ? opts->forced_dt[0] : 0.0;
+      if (blind) { su.targets = S.p.targets; su.target = (double)(dec ? -t_pts[n_t - 2] : t_pts[n_t - 2]); }
+    }
+    TRY(S.prepare(&su));
+  }
   const int w4_gskew = env_int("NODE_TUNE_W4_GSKEW", 0);           // diagnostics (include/node_hip.h, node_w4_pair_stats)
   const bool w4_stats = env_int("NODE_TUNE_W4_STATS", 0) != 0;
   g_w4_pair_stats[0] = S.w4_f16 ? 1 : 0; g_w4_pair_stats[1] = -1; g_w4_pair_stats[2] = 0; g_w4_pair_stats[3] = 0;
-  launch_set_ctrl(S.p.ctrl, 0.0, 0.0, 1, S.st);  // also zeroes the scalar segment (adj_time = 0)
-  launch_fill(S.p.TH, 0.f, S.d.P, S.st);         // adj_params = 0
   // grad_last_only: `grad_out` is the last slice alone, every other slice of dL/dy_out is zero (node_solve_opts)
   const bool last_only = opts && opts->grad_last_only;
   const float* g_last = last_only ? grad_out : grad_out + (size_t)(n_t - 1) * numel;
-  S.to_state(g_last, S.p.A);  // adj_y = grad_output[-1]
+  if (S.w4) {     // adj_y = grad_output[-1] and the first interval's y = y_traj[-1]: one launch, two jobs
+    W4sLayoutJobs lj;
+    memset(&lj, 0, sizeof(lj));
+    lj.src[0] = g_last; lj.dst[0] = S.p.A; lj.src[1] = y_traj + (size_t)(n_t - 1) * numel; lj.dst[1] = S.p.Y; lj.njobs = 2;
+    launch_w4s_from_nchw_jobs(lj, S.d.N, S.d.C, S.d.w4q, S.st);
+  } else {
+    S.to_state(g_last, S.p.A);  // adj_y = grad_output[-1]
+  }
   if (forced) TRY(S.upload(S.p.forced, opts->forced_dt, opts->n_forced_dt, hs->lists + n_t));
   double cur_t = 0.0, cur_dt = 0.0;
   bool first = true;
@@ -228,7 +265,7 @@ int node_solve_adjoint(const node_shape* shape, const node_params* params, const
     const double s0 = (double)(decreasing ? -t_pts[i] : t_pts[i]);
     const double s1 = (double)(decreasing ? -t_pts[i - 1] : t_pts[i - 1]);
 
-    S.to_state(y_traj + (size_t)i * numel, S.p.Y);
+    if (!(S.w4 && i == n_t - 1)) S.to_state(y_traj + (size_t)i * numel, S.p.Y);
     // grad_output_i in NHWC for the dot product below: in the first interval the adjoint state still IS it; a zero
     // slice (grad_last_only) contributes nothing
     const float* gdot = i == n_t - 1 ? S.p.A : (last_only ? nullptr : S.p.G);
@@ -248,8 +285,9 @@ int node_solve_adjoint(const node_shape* shape, const node_params* params, const
       cur_t = s1; cur_dt = s1 - s0;
     } else {
       // replay list restarts per interval (one odeint call each upstream)
-      launch_set_interval(S.p.ctrl, s0, forced ? opts->forced_dt[0] : 0.0, S.st);
-      if (blind) launch_set_target(S.p.targets, s1, S.st);
+      const bool rode = i == n_t - 1;     // (the first interval's setters rode in the preparation launch)
+      if (!rode) launch_set_interval(S.p.ctrl, s0, forced ? opts->forced_dt[0] : 0.0, S.st);
+      if (blind) { if (!rode) launch_set_target(S.p.targets, s1, S.st); }
       else TRY(S.upload(S.p.targets, &s1, 1, hs->lists + (n_t - 1 - i) % n_t));
       S.g_ready = false;      // (fp16-pair operands: the interval's first evaluation runs the triples and records max|dz|, wino4.h)
       TRY(S.eval_sys(0, nullptr, 0, SC_ABS, S.et_stage(0.0), false));
@@ -257,8 +295,11 @@ int node_solve_adjoint(const node_shape* shape, const node_params* params, const
       if (gdot) launch_dot_sub_scalar(S.p.ctrl, S.p.KY[0], gdot, numel, S.tsign, S.p.partial[0], dots_i, S.st);
       if (!forced) TRY(S.initial_step());
       if (blind) {   // deferred completion (one interval): the record says later whether these were the steps needed
-        for (int q = 0; q < blind; ++q) TRY(S.enqueue_step(io));
-        launch_export_record(S.p.ctrl, opts->record, opts->miss_flag, blind, S.st);
+        for (int q = 0; q < blind; ++q) {
+          if (q == blind - 1) { io.rec = opts->record; io.miss_flag = opts->miss_flag; io.expect_steps = blind; }   // (the record rides in the last commit)
+          TRY(S.enqueue_step(io));
+        }
+        io.rec = nullptr; io.miss_flag = nullptr;
         steps_total += blind;
         stt.accepted = blind; stt.rejected = 0; stt.status = 0;
         cur_t = s1; cur_dt = 0.0;

@@ -112,17 +112,46 @@ void launch_wtime(const Dims& d, const float* w, float* wtime, hipStream_t s) {
 
 // Both layers' border maps (and, for an augmented solve, their gathered time-channel taps) in ONE launch per solve:
 // blockIdx.y = job.  Four to six launches of ~4.5 us each (their floor on this box) per training step otherwise.
-struct TimePrepArgs { const float* w[2]; float* tmap[2]; float* wtime[2]; float* zero[12]; size_t zero_n[12]; int nzero; int njobs; };
+// An F(4x4,3x3) solve also gets both maps in the blocking its forward passes read (tmapS: [Q quadrants][C/16][4 i][64 lanes][4 j],
+// kernels_w4s.hip) from two more jobs of the same launch -- the same nine-tap sum in the same order, written at the W4S position
+// (it used to be a launch of its own that permuted tmap).
+struct TimePrepArgs { const float* w[2]; float* tmap[2]; float* wtime[2]; float* tmapS[2]; int Q; float* zero[12]; size_t zero_n[12]; int nzero; int njobs; int nsjobs; int nset; SolveSetup set; };
 __global__ __launch_bounds__(256) void k_time_prep(TimePrepArgs a, int C, int H, int W) {
   const int job = blockIdx.y, layer = job & 1;
-  if (job >= a.njobs) {   // the solve's zero fills (zero rows behind the conv inputs, the never-written stage derivative,
-                          // the finalize kernel's arrival counter): they used to be one hipMemsetAsync each
-    const int z = job - a.njobs;
+  if (job == a.njobs + a.nsjobs + a.nzero) {   // (nset = 1) the solve's scalar set-up (SolveSetup): one thread, in the launches' order
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      if (a.set.set_ctrl) ctrl_set(a.set.ctrl, a.set.t, a.set.dt, 1);
+      if (a.set.set_interval) ctrl_set_interval(a.set.ctrl, a.set.iv_t, a.set.iv_dt);
+      if (a.set.targets != nullptr) a.set.targets[0] = a.set.target;
+    }
+    return;
+  }
+  if (job >= a.njobs + a.nsjobs) {   // the solve's zero fills (zero rows behind the conv inputs, the never-written stage derivative,
+                                     // the finalize kernel's arrival counter): they used to be one hipMemsetAsync each
+    const int z = job - a.njobs - a.nsjobs;
     float* p = a.zero[z];
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.zero_n[z]; i += (size_t)gridDim.x * blockDim.x) p[i] = 0.f;
     return;
   }
   const float* w = a.w[layer];
+  if (job >= a.njobs) {   // tmapS (njobs is even: layer = job & 1): H = W = 8 (Q = 1) or 16 (Q = 4)
+    float* out = a.tmapS[layer];
+    const int CB = C >> 4;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < 64 * a.Q * C; idx += gridDim.x * blockDim.x) {
+      const int j = idx & 3, lane = (idx >> 2) & 63, i = (idx >> 8) & 3, rest = idx >> 10;
+      const int q = rest / CB, cb = rest - q * CB;
+      const int t = lane >> 4, co = cb * 16 + (lane & 15);
+      const int h = 8 * (q >> 1) + 4 * (t >> 1) + i, x = 8 * (q & 1) + 4 * (t & 1) + j;
+      float sum = 0.f;
+      for (int kh = 0; kh < 3; ++kh)
+        for (int kw = 0; kw < 3; ++kw) {
+          const int hh = h + kh - 1, ww = x + kw - 1;
+          if (hh >= 0 && hh < H && ww >= 0 && ww < W) sum += w[(((size_t)co * (C + 1)) * 3 + kh) * 3 + kw];
+        }
+      out[idx] = sum;
+    }
+    return;
+  }
   if (job < 2) {
     float* tmap = a.tmap[layer];
     const int HW = H * W;
@@ -146,17 +175,21 @@ __global__ __launch_bounds__(256) void k_time_prep(TimePrepArgs a, int C, int H,
   }
 }
 void launch_time_prep(const Dims& d, const float* w1, const float* w2, float* tmap1, float* tmap2, float* wtime1, float* wtime2,
-                      float* const* zero, const size_t* zero_n, int nzero, hipStream_t s) {
+                      float* const* zero, const size_t* zero_n, int nzero, hipStream_t s, float* tmapS1, float* tmapS2, int Q,
+                      const SolveSetup* setup) {
   TimePrepArgs a;
   memset(&a, 0, sizeof(a));
   a.w[0] = w1; a.w[1] = w2; a.tmap[0] = tmap1; a.tmap[1] = tmap2; a.wtime[0] = wtime1; a.wtime[1] = wtime2;
   a.njobs = wtime1 != nullptr ? 4 : 2;
-  a.nzero = nzero > 12 ? 12 : nzero;
+  a.tmapS[0] = tmapS1; a.tmapS[1] = tmapS2; a.Q = Q; a.nsjobs = tmapS1 != nullptr ? 2 : 0;
+  if (nzero > 12) abort();     // (zero[12]: a dropped fill would be a silent wrong answer; Solver::prepare counts before it calls)
+  a.nzero = nzero;
   for (int i = 0; i < a.nzero; ++i) { a.zero[i] = zero[i]; a.zero_n[i] = zero_n[i]; }
+  if (setup != nullptr) { a.set = *setup; a.nset = 1; }
   const int total = d.HW * d.C;
   int bx = (total + 255) / 256;
   if (bx > 256) bx = 256;
-  hipLaunchKernelGGL(k_time_prep, dim3(bx, a.njobs + a.nzero), dim3(256), 0, s, a, d.C, d.H, d.W);
+  hipLaunchKernelGGL(k_time_prep, dim3(bx, a.njobs + a.nsjobs + a.nzero + a.nset), dim3(256), 0, s, a, d.C, d.H, d.W);
 }
 
 // ---------------------------------------------- theta internal -> PyTorch flat

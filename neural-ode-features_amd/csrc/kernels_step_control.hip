@@ -281,19 +281,7 @@ void launch_init_controller(const InitCtlArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_init_controller, dim3(1), dim3(256), 0, s, a);
 }
 
-__global__ void k_set_ctrl(Ctrl* c, double t, double dt, int reset) {
-  c->t = t;
-  c->dt = dt;
-  c->t_prev = t;
-  c->dt_used = 0.0;
-  c->done = 0; c->step_idx = 0; c->j = 0; c->j0 = 0; c->j1 = 0; c->first_dt = 0.0;
-  if (reset) {
-    c->accept = 0; c->status = 0; c->n_acc = 0; c->n_rej = 0; c->h0 = 0.f; c->d0 = 0.f; c->d1 = 0.f;
-    for (int i = 0; i < 4; ++i) c->ratio[i] = 0.f;
-    c->ts_cur = 0.f; c->ts_new = 0.f; c->ts_y0_prev = 0.f; c->ts_f0_prev = 0.f;
-    for (int i = 0; i < 7; ++i) c->ts_k[i] = 0.f;
-  }
-}
+__global__ void k_set_ctrl(Ctrl* c, double t, double dt, int reset) { ctrl_set(c, t, dt, reset); }
 void launch_set_ctrl(Ctrl* ctrl, double t, double dt, int reset, hipStream_t s) {
   hipLaunchKernelGGL(k_set_ctrl, dim3(1), dim3(1), 0, s, ctrl, t, dt, reset);
 }
@@ -393,8 +381,10 @@ void launch_flat_scalar(Ctrl* ctrl, int which, const float* src, float scale, in
 
 // Accepted step, interval not finished: y <- y1, k0 <- k6 (FSAL) for every tensor segment.  Augmented solve at the
 // end of its interval: every segment <- dense output at the interval's end time, in place (element-wise).
+__device__ inline void export_record(const Ctrl* c, node_step_record* r, float* miss_flag, int expect);
 __global__ __launch_bounds__(256) void k_commit(CommitArgs a) {
   const Ctrl* c = a.ctrl;
+  if (a.rec != nullptr && blockIdx.x == 0 && threadIdx.x == 0) export_record(c, a.rec, a.miss_flag, a.expect_steps);
   if (!c->accept || c->step_idx == 0) return;
   const bool fin = c->done != 0;
   if (fin && !(a.interp_final && c->j1 > c->j0 && c->status == 0)) return;
@@ -439,19 +429,17 @@ void launch_set_target(double* targets, double t_end, hipStream_t s) {
 // Deferred completion: what the host would have read back, left in the caller's device record; a miss (the steps
 // enqueued did not finish the interval, or it stopped with a status) also bumps the caller's flag, on which the
 // optimizer step is predicated.
-__global__ void k_export_record(const Ctrl* c, node_step_record* r, float* miss_flag, int expect) {
+__device__ inline void export_record(const Ctrl* c, node_step_record* r, float* miss_flag, int expect) {
   const int miss = !(c->done && c->status == 0 && c->step_idx <= expect);   // (steps past the end did nothing)
   r->done = c->done; r->status = c->status; r->steps = c->step_idx; r->accepted = c->n_acc; r->rejected = c->n_rej;
   r->miss = miss; r->t = c->t; r->dt = c->dt; r->first_dt = c->first_dt; r->t_prev = c->t_prev; r->dt_used = c->dt_used;
   if (miss && miss_flag != nullptr) *miss_flag += 1.f;
 }
+__global__ void k_export_record(const Ctrl* c, node_step_record* r, float* miss_flag, int expect) { export_record(c, r, miss_flag, expect); }
 void launch_export_record(const Ctrl* ctrl, node_step_record* rec, float* miss_flag, int expect_steps, hipStream_t s) {
   hipLaunchKernelGGL(k_export_record, dim3(1), dim3(1), 0, s, ctrl, rec, miss_flag, expect_steps);
 }
-__global__ void k_set_interval(Ctrl* c, double t, double dt) {
-  c->t = t; c->dt = dt; c->t_prev = t; c->dt_used = 0.0;
-  c->done = 0; c->step_idx = 0; c->j = 0; c->j0 = 0; c->j1 = 0; c->first_dt = 0.0; c->accept = 0;
-}
+__global__ void k_set_interval(Ctrl* c, double t, double dt) { ctrl_set_interval(c, t, dt); }
 void launch_set_interval(Ctrl* ctrl, double t, double dt, hipStream_t s) {
   hipLaunchKernelGGL(k_set_interval, dim3(1), dim3(1), 0, s, ctrl, t, dt);
 }

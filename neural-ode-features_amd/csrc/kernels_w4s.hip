@@ -38,7 +38,7 @@
 // a workgroup holds the four quadrant waves of a (sample, GroupNorm group set) -- 4 waves for cpg <= 16, 8 for cpg = 32
 // -- the GroupNorm sums cross the waves through LDS (one barrier per sum, two alternating slots), and the pixel ring of
 // the input transform comes out of an LDS copy of the workgroup's tiles instead of nine shuffles.
-#include "wino4.h"
+#include "theta_finalize.h"
 #include <cstring>
 
 namespace node {
@@ -520,21 +520,22 @@ __device__ __forceinline__ void w4s_gn_bwd(const float g[4][4], const float xh[4
 
 // the wave's place in the launch (see W4Wave): Q = 1 -> independent waves, W4S_THREADS / 64 per workgroup;
 // Q = 4 -> workgroup = (sample, NB consecutive 16-channel blocks) x four quadrants, NB = blockDim / 256
+// `block`: the workgroup's index among the pass's own (a launch that carries a rider has other workgroups in front)
 template <int Q>
-__device__ __forceinline__ void w4s_place(W4Wave<Q>& wv, int C, float* red, float* tiles) {
+__device__ __forceinline__ void w4s_place(W4Wave<Q>& wv, int C, float* red, float* tiles, int block) {
   const int CB = C >> 4;
   wv.lane = threadIdx.x & 63;
   wv.t = wv.lane >> 4; wv.c15 = wv.lane & 15; wv.ty = wv.t >> 1; wv.tx = wv.t & 1;
   wv.w = threadIdx.x >> 6; wv.slot = 0; wv.red = red; wv.tiles = tiles;
   if (Q == 1) {
-    const int unit = blockIdx.x * (blockDim.x >> 6) + wv.w;
+    const int unit = block * (blockDim.x >> 6) + wv.w;
     wv.n = unit / CB; wv.cb = unit - wv.n * CB;
     wv.q = 0; wv.nv = wv.n; wv.nw = 1;
     wv.TY = wv.ty; wv.TX = wv.tx; wv.TM = 1;
   } else {
     const int NB = blockDim.x >> 8, GS = CB / NB;
-    wv.n = blockIdx.x / GS;
-    wv.cb = (blockIdx.x - wv.n * GS) * NB + (wv.w >> 2);
+    wv.n = block / GS;
+    wv.cb = (block - wv.n * GS) * NB + (wv.w >> 2);
     wv.q = wv.w & 3; wv.nv = 4 * wv.n + wv.q; wv.nw = 4 * NB;
     wv.TY = 2 * (wv.q >> 1) + wv.ty; wv.TX = 2 * (wv.q & 1) + wv.tx; wv.TM = 3;
   }
@@ -570,147 +571,29 @@ __device__ __forceinline__ void w4s_put_v(const float v[4][4], const W4Wave<Q>& 
 template <int HEAD, int TAIL, int Q>
 __global__ __launch_bounds__(Q == 1 ? W4S_THREADS : 512) void k_w4s_pass(W4sArgs a) {
   if (a.ctrl != nullptr && a.ctrl->done) return;   // a step enqueued past the end of the interval (Ctrl::done)
-  __shared__ float s_red[Q == 4 ? W4Q_RED : 1];
-  __shared__ float s_tiles[Q == 4 ? W4Q_TILES : 1];
-  W4Wave<Q> wv;
-  w4s_place(wv, a.C, s_red, s_tiles);
-  const int lane = wv.lane, CB = a.C >> 4, n = wv.n, cb = wv.cb, t = wv.t, c = wv.c;
-  const int cpg = a.cpg, G = a.C / cpg, grp = c / cpg;
-  const float inv_m = 1.0f / (float)(64 * Q * cpg);
-  const size_t f4 = ((size_t)wv.nv * CB + cb) * 256 + lane;   // float4 index of tile row 0 in a W4S tensor (rows 64 apart)
-  const bool stat_lane = t == 0 && wv.q == 0 && c % cpg == 0;   // the one lane of the launch that owns (sample, group)
+  const int block = blockIdx.x;
+#include "w4s_pass_body.inc"
+}
 
-  float v[4][4];     // the conv input whose transform leaves at the end
-  float hx[4][4];    // HEAD 1: xhat of the head's GroupNorm
-  float ho[4][4];    // the head's output (a stage derivative)
-  float hrstd = 0.f;
-
-  if (HEAD == 1) {
-    const W4sHead& h = a.h;
-    float z[4][4];
-    w4s_out_transform(w4s_m_ptr(h.M, wv, a.C), z);
-    const float tval = eval_time(h.et), bv = h.bias[c];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float4 tm = w4s_ld4(h.tmapS, ((size_t)wv.q * CB + cb) * 256 + i * 64 + lane);
-      z[i][0] += fmaf(tval, tm.x, bv); z[i][1] += fmaf(tval, tm.y, bv); z[i][2] += fmaf(tval, tm.z, bv); z[i][3] += fmaf(tval, tm.w, bv);
-    }
-    float mean;
-    w4s_gn_stats(z, cpg, inv_m, a.eps, wv, mean, hrstd);
-    const float gam = h.gamma[c], bet = h.beta[c];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        hx[i][j] = (z[i][j] - mean) * hrstd;
-        float vv = fmaf(hx[i][j], gam, bet);
-        if (h.relu) vv = fmaxf(vv, 0.f);
-        ho[i][j] = h.osign * vv;
-      }
-    if (h.out_s) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w4s_st4(h.out_s, f4 + i * 64, ho[i]);
-    }
-    if (h.out_nhwc) w4s_store_nhwc(h.out_nhwc, wv, a.C, ho);
-    if (h.xhat_s) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w4s_st4(h.xhat_s, f4 + i * 64, hx[i]);
-    }
-    if (h.rstd && stat_lane) h.rstd[(size_t)n * G + grp] = hrstd;
-    if (TAIL == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = ho[i][j];
-    }
+// P2 with a RIDER: the theta finalize of the evaluation in front (theta_finalize.h; Solver::eval_w4 says why nothing it reads or
+// writes meets this pass) as the first r.blocks workgroups of the grid -- first, so that its chains of dependent round trips start
+// with the launch -- and the pass's own workgroups behind them.  Both honour ctrl->done as their own launches do.
+// Workgroup size: the pass's -- W4S_THREADS (Q = 1) or 256 (Q = 4, cpg <= 16); Q = 4 with 512-thread workgroups has no rider.
+// Registers (gfx950, -Rpass-analysis=kernel-resource-usage): 125 (Q = 1) / 137 (Q = 4) VGPRs against the plain P2's 74 / 72, no
+// scratch, 4 / 3 waves per SIMD -- cfg 2's P2 is 2 048 pass waves + 616 of the rider on 1 024 SIMDs: one generation either way.
+// (amdgpu_waves_per_eu: never fewer than two, whatever a later change does to the finalize.)
+constexpr int W4S_RIDER_THREADS_Q1 = W4S_THREADS, W4S_RIDER_THREADS_Q4 = 256;
+static_assert(W4S_THREADS == 128 || W4S_THREADS == 256, "theta_finalize_body takes 128 or 256 threads");
+template <int Q>
+__global__ __launch_bounds__(Q == 1 ? W4S_RIDER_THREADS_Q1 : W4S_RIDER_THREADS_Q4) __attribute__((amdgpu_waves_per_eu(2))) void k_w4s_pass_rider(W4sArgs a, W4sRider r) {
+  if (a.ctrl != nullptr && a.ctrl->done) return;
+  if ((int)blockIdx.x < r.blocks) {
+    theta_finalize_body<(Q == 1 ? W4S_RIDER_THREADS_Q1 : W4S_RIDER_THREADS_Q4)>(r.tf, r.d, blockIdx.x, r.blocks);
+    return;
   }
-  if (HEAD == 2) {
-    const W4sHead& h = a.h;
-    float4 xq[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) xq[i] = w4s_ld4(h.xhat_s, f4 + i * 64);
-    const float gam = h.gamma[c], bet = h.beta[c], rs = h.rstd[(size_t)n * G + grp];
-    float g[4][4], xh[4][4];
-    w4s_out_transform(w4s_m_ptr(h.M, wv, a.C), g);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      xh[i][0] = xq[i].x; xh[i][1] = xq[i].y; xh[i][2] = xq[i].z; xh[i][3] = xq[i].w;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[i][j] = fmaf(xh[i][j], gam, bet) > 0.f ? g[i][j] : 0.f;   // ReLU mask of this layer's output
-    }
-    w4s_gn_bwd(g, xh, gam, rs, cpg, inv_m, h.osign, wv, a.C, h.gpart, ho);
-    if (h.out_s) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w4s_st4(h.out_s, f4 + i * 64, ho[i]);
-    }
-    if (h.out_nhwc) w4s_store_nhwc(h.out_nhwc, wv, a.C, ho);
-    if (h.spart) w4s_colsums(ho, wv, h.spart, a.C);
-    if (a.gstat != nullptr && (h.z_out != nullptr || (TAIL == 0 && a.V != nullptr))) w4s_record_max(ho, a.gstat, a.z_exp != nullptr ? a.z_exp : (TAIL == 0 ? a.v_exp : nullptr));
-    if (h.z_out) {
-      if (a.z_exp != nullptr) w4s_emit_zh(ho, w4s_vh_ptr(h.z_out, wv, a.C), (size_t)4 * a.Nv * a.C, ldexpf(1.f, *a.z_exp), (wv.c15 & 1) != 0);
-      else w4s_emit_z(ho, wv.nv, a.Nv, a.C, c, t, h.z_out);
-    }
-    if (TAIL == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[i][j] = ho[i][j];
-    }
-  }
-
-  if (TAIL != 0) {
-    const W4sTail& tl = a.t;
-    const float scale = comb_scale(tl.comb, a.ctrl);
-    float cf[7];
-#pragma unroll
-    for (int j = 0; j < 7; ++j) cf[j] = scale * tl.comb.coef[j];
-    float y[4][4];
-    if (HEAD == 1 && TAIL == 1) {
-      if (tl.self) w4s_comb_any<true>(tl.comb, cf, f4, ho, y);
-      else w4s_comb_any<false>(tl.comb, cf, f4, ho, y);
-    } else {
-      w4s_comb_any<false>(tl.comb, cf, f4, ho, y);
-    }
-    if (tl.y_out) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) w4s_st4(tl.y_out, f4 + i * 64, y[i]);
-    }
-    if (TAIL == 1) {   // GroupNorm-1 -> ReLU (model.py:341-342)
-      float mean, rstd;
-      w4s_gn_stats(y, cpg, inv_m, a.eps, wv, mean, rstd);
-      const float gam = tl.gamma[c], bet = tl.beta[c];
-      float xh[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          xh[i][j] = (y[i][j] - mean) * rstd;
-          v[i][j] = fmaxf(fmaf(xh[i][j], gam, bet), 0.f);
-        }
-      if (tl.act_nhwc) w4s_store_nhwc(tl.act_nhwc, wv, a.C, v);
-      if (tl.xhat_s) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) w4s_st4(tl.xhat_s, f4 + i * 64, xh[i]);
-      }
-      if (tl.rstd && stat_lane) tl.rstd[(size_t)n * G + grp] = rstd;
-    } else {   // cotangent g = csign * (adjoint combine) through GroupNorm-3's backward (xhat-3, 1/sigma-3 from the head)
-      float g[4][4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) g[i][j] = tl.csign * y[i][j];
-      w4s_gn_bwd(g, hx, a.h.gamma[c], hrstd, cpg, inv_m, 1.f, wv, a.C, tl.gpart, v);
-      if (tl.act_nhwc) w4s_store_nhwc(tl.act_nhwc, wv, a.C, v);
-      if (tl.spart) w4s_colsums(v, wv, tl.spart, a.C);
-      if (a.gstat != nullptr) w4s_record_max(v, a.gstat, a.z_exp != nullptr ? a.z_exp : a.v_exp);
-      if (tl.z_out) {
-        if (a.z_exp != nullptr) w4s_emit_zh(v, w4s_vh_ptr(tl.z_out, wv, a.C), (size_t)4 * a.Nv * a.C, ldexpf(1.f, *a.z_exp), (wv.c15 & 1) != 0);
-        else w4s_emit_z(v, wv.nv, a.Nv, a.C, c, t, tl.z_out);
-      }
-    }
-  }
-
-  if (a.V != nullptr) w4s_put_v(v, wv, a.V, a.C, a.Nv, a.v_exp);
+  constexpr int HEAD = 1, TAIL = 0;
+  const int block = (int)blockIdx.x - r.blocks;
+#include "w4s_pass_body.inc"
 }
 
 // workgroups of the Q = 4 kernels: (sample, NB consecutive 16-channel blocks) x four quadrants, NB = 2 when a GroupNorm
@@ -741,6 +624,20 @@ void launch_w4s_pass(int head, int tail, const W4sArgs& a, hipStream_t s) {
   else if (head == 2 && tail == 0) W4S_GO(2, 0)
   else if (head == 2 && tail == 1) W4S_GO(2, 1)
 #undef W4S_GO
+}
+
+bool w4s_rider_fits(int cpg, int Q) { return Q == 1 || cpg <= 16; }
+
+void launch_w4s_p2_rider(const W4sArgs& a, const ThetaFinalizeArgs& tf, const Dims& d, hipStream_t s) {
+  static_assert(sizeof(W4sArgs) + sizeof(W4sRider) <= 4096, "kernel arguments");
+  dim3 grid, block;
+  w4s_grid(a.N, a.C, a.cpg, a.Q, grid, block);
+  W4sRider r;
+  memset(&r, 0, sizeof(r));
+  r.tf = tf; r.d = d; r.blocks = (int)theta_finalize_blocks(d, tf);
+  grid.x += (unsigned)r.blocks;
+  if (a.Q == 1) hipLaunchKernelGGL(k_w4s_pass_rider<1>, grid, block, 0, s, a, r);
+  else hipLaunchKernelGGL(k_w4s_pass_rider<4>, grid, block, 0, s, a, r);
 }
 
 // ----------------------------------------------------------------------------
@@ -776,26 +673,28 @@ static void w4s_layout(const float* src, float* dst, int N, int C, int Q, int to
   if (Q == 1) hipLaunchKernelGGL(k_w4s_layout<1>, grid, block, 0, s, reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), total, C >> 4, to_nchw);
   else hipLaunchKernelGGL(k_w4s_layout<4>, grid, block, 0, s, reinterpret_cast<const float4*>(src), reinterpret_cast<float4*>(dst), total, C >> 4, to_nchw);
 }
+// NCHW -> W4S for up to two tensors of one shape in ONE launch (blockIdx.y = job), each with up to two straight copies of the
+// source on the way (a forward solve's y0 -> its state, and -> the trajectory's first slot and a deferred solve's output slot)
+template <int Q>
+__global__ __launch_bounds__(256) void k_w4s_layout_jobs(W4sLayoutJobs j, size_t total, int CB) {
+  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;
+  const bool second = blockIdx.y != 0;
+  const float4 v = reinterpret_cast<const float4*>(second ? j.src[1] : j.src[0])[idx];
+  reinterpret_cast<float4*>(second ? j.dst[1] : j.dst[0])[w4s_of_nchw<Q>(idx, CB)] = v;
+  float* c0 = second ? j.copy[1][0] : j.copy[0][0];
+  float* c1 = second ? j.copy[1][1] : j.copy[0][1];
+  if (c0 != nullptr) reinterpret_cast<float4*>(c0)[idx] = v;
+  if (c1 != nullptr) reinterpret_cast<float4*>(c1)[idx] = v;
+}
+void launch_w4s_from_nchw_jobs(const W4sLayoutJobs& j, int N, int C, int Q, hipStream_t s) {
+  const size_t total = (size_t)N * C * 16 * Q;
+  const dim3 grid((unsigned)((total + 255) / 256), j.njobs), block(256);
+  if (Q == 1) hipLaunchKernelGGL(k_w4s_layout_jobs<1>, grid, block, 0, s, j, total, C >> 4);
+  else hipLaunchKernelGGL(k_w4s_layout_jobs<4>, grid, block, 0, s, j, total, C >> 4);
+}
 void launch_w4s_from_nchw(const float* src, float* dst, int N, int C, int Q, hipStream_t s) { w4s_layout(src, dst, N, C, Q, 0, s); }
 void launch_w4s_to_nchw(const float* src, float* dst, int N, int C, int Q, hipStream_t s) { w4s_layout(src, dst, N, C, Q, 1, s); }
-
-// border-aware time-channel map [HW][C] -> the W4S blocking ([Q quadrants][C/16][4 i][64 lanes][4 j]) the forward passes read
-__global__ __launch_bounds__(256) void k_w4s_tmap(const float* __restrict__ tmap0, const float* __restrict__ tmap1, float* __restrict__ out0,
-                                                  float* __restrict__ out1, int C, int Q) {
-  const float* tm = blockIdx.y ? tmap1 : tmap0;
-  float* out = blockIdx.y ? out1 : out0;
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= 64 * Q * C) return;
-  const int CB = C >> 4, WI = Q == 4 ? 16 : 8;
-  const int j = idx & 3, lane = (idx >> 2) & 63, i = (idx >> 8) & 3, rest = idx >> 10;
-  const int q = rest / CB, cb = rest - q * CB;
-  const int t = lane >> 4, c = cb * 16 + (lane & 15);
-  const int p = (8 * (q >> 1) + 4 * (t >> 1) + i) * WI + 8 * (q & 1) + 4 * (t & 1) + j;
-  out[idx] = tm[(size_t)p * C + c];
-}
-void launch_w4s_tmap(const float* tmap0, const float* tmap1, float* out0, float* out1, int C, int Q, hipStream_t s) {
-  hipLaunchKernelGGL(k_w4s_tmap, dim3((64 * Q * C + 255) / 256, 2), dim3(256), 0, s, tmap0, tmap1, out0, out1, C, Q);
-}
 
 // Dense output of the forward solve (k_emit_outputs) for W4S state: element-wise on the 16-B vectors, written at their
 // NCHW position.
@@ -847,7 +746,7 @@ __global__ __launch_bounds__(Q == 1 ? W4S_THREADS : 512) void k_w4s_input(const 
                                                                           const int* v_exp) {
   __shared__ float s_tiles[Q == 4 ? W4Q_TILES : 1];
   W4Wave<Q> wv;
-  w4s_place(wv, C, nullptr, s_tiles);
+  w4s_place(wv, C, nullptr, s_tiles, blockIdx.x);
   const size_t f4 = ((size_t)wv.nv * (C >> 4) + wv.cb) * 256 + wv.lane;
   float v[4][4];
 #pragma unroll
@@ -860,7 +759,7 @@ __global__ __launch_bounds__(Q == 1 ? W4S_THREADS : 512) void k_w4s_input(const 
 template <int Q>
 __global__ __launch_bounds__(Q == 1 ? W4S_THREADS : 512) void k_w4s_output(const float* __restrict__ M, float* __restrict__ y, int C) {
   W4Wave<Q> wv;
-  w4s_place(wv, C, nullptr, nullptr);
+  w4s_place(wv, C, nullptr, nullptr, blockIdx.x);
   const size_t f4 = ((size_t)wv.nv * (C >> 4) + wv.cb) * 256 + wv.lane;
   float z[4][4];
   w4s_out_transform(w4s_m_ptr(M, wv, C), z);
@@ -892,7 +791,7 @@ __global__ __launch_bounds__(W4S_THREADS) void k_w4s_stem_in(const float* __rest
                                                              const float* __restrict__ beta, float eps, int cpg, float* __restrict__ xhat_s,
                                                              float* __restrict__ rstd, float* __restrict__ V, int C, int Nv) {
   W4Wave<1> wv;
-  w4s_place(wv, C, nullptr, nullptr);
+  w4s_place(wv, C, nullptr, nullptr, blockIdx.x);
   const float* base = h + ((size_t)wv.n * 64 + (4 * wv.TY) * 8 + 4 * wv.TX) * C + wv.c;
   float y[4][4];
 #pragma unroll
@@ -919,7 +818,7 @@ __global__ __launch_bounds__(W4S_THREADS) void k_w4s_stem_in(const float* __rest
 // M -> A^T M A + shortcut (NHWC) -> the stem's output, NCHW
 __global__ __launch_bounds__(W4S_THREADS) void k_w4s_stem_out(const float* __restrict__ M, const float* __restrict__ res, float* __restrict__ out, int C) {
   W4Wave<1> wv;
-  w4s_place(wv, C, nullptr, nullptr);
+  w4s_place(wv, C, nullptr, nullptr, blockIdx.x);
   float z[4][4];
   w4s_out_transform(w4s_m_ptr(M, wv, C), z);
   const float* rb = res + ((size_t)wv.n * 64 + (4 * wv.TY) * 8 + 4 * wv.TX) * C + wv.c;
@@ -937,7 +836,7 @@ __global__ __launch_bounds__(W4S_THREADS) void k_w4s_stem_out(const float* __res
 // dL/d out (NCHW) -> its row operand V (for the data gradient) and Z = A g A^T (for the weight gradient)
 __global__ __launch_bounds__(W4S_THREADS) void k_w4s_stem_gin(const float* __restrict__ g, float* __restrict__ V, float* __restrict__ Z, int C, int Nv) {
   W4Wave<1> wv;
-  w4s_place(wv, C, nullptr, nullptr);
+  w4s_place(wv, C, nullptr, nullptr, blockIdx.x);
   const float* gb = g + ((size_t)wv.n * C + wv.c) * 64 + (4 * wv.TY) * 8 + 4 * wv.TX;
   float v[4][4];
 #pragma unroll

@@ -109,6 +109,35 @@ struct Ctrl {
   double first_dt; // step size of the interval's first step
 };
 
+// what k_set_ctrl / k_set_interval store (kernels_step_control.hip), for every launch that carries them
+__device__ inline void ctrl_set(Ctrl* c, double t, double dt, int reset) {
+  c->t = t;
+  c->dt = dt;
+  c->t_prev = t;
+  c->dt_used = 0.0;
+  c->done = 0; c->step_idx = 0; c->j = 0; c->j0 = 0; c->j1 = 0; c->first_dt = 0.0;
+  if (reset) {
+    c->accept = 0; c->status = 0; c->n_acc = 0; c->n_rej = 0; c->h0 = 0.f; c->d0 = 0.f; c->d1 = 0.f;
+    for (int i = 0; i < 4; ++i) c->ratio[i] = 0.f;
+    c->ts_cur = 0.f; c->ts_new = 0.f; c->ts_y0_prev = 0.f; c->ts_f0_prev = 0.f;
+    for (int i = 0; i < 7; ++i) c->ts_k[i] = 0.f;
+  }
+}
+__device__ inline void ctrl_set_interval(Ctrl* c, double t, double dt) {
+  c->t = t; c->dt = dt; c->t_prev = t; c->dt_used = 0.0;
+  c->done = 0; c->step_idx = 0; c->j = 0; c->j0 = 0; c->j1 = 0; c->first_dt = 0.0; c->accept = 0;
+}
+// The scalar set-up of a solve that precedes every consumer rides in the preparation launch (k_time_prep's last job) instead of
+// one-thread launches of its own: k_set_ctrl(reset = 1), then k_set_interval, then targets[0] = target -- in this order, each
+// only when asked for -- and one more zero fill (the adjoint's parameter segment).
+struct SolveSetup {
+  Ctrl* ctrl;
+  int set_ctrl; double t, dt;              // launch_set_ctrl(ctrl, t, dt, 1)
+  int set_interval; double iv_t, iv_dt;    // launch_set_interval(ctrl, iv_t, iv_dt)
+  double* targets; double target;          // launch_set_target(targets, target); nullable
+  float* zero; size_t zero_n;              // launch_fill(zero, 0.f, zero_n); nullable
+};
+
 enum TimeMode { TM_STAGE = 0, TM_PROBE = 1 };
 
 // how an eval derives its time:  t_real = tsign * ((float)t + (mode==TM_STAGE ? alpha*(float)dt : h0))
@@ -182,9 +211,11 @@ void launch_nhwc_to_nchw(const Dims& d, const float* src, float* dst, hipStream_
 void launch_pack_weights(const Dims& d, const float* w /*[C][C+1][3][3]*/, float* packed, int dgrad, hipStream_t s);
 void launch_tmap(const Dims& d, const float* w, float* tmap /*[HW][C]*/, hipStream_t s);
 void launch_wtime(const Dims& d, const float* w, float* wtime /*[9][C]*/, hipStream_t s);
-// tmap of both layers (+ wtime of both when wtime1 != nullptr) in one launch
+// tmap of both layers (+ wtime of both when wtime1 != nullptr; + both maps in the F(4x4,3x3) passes' blocking, Q quadrants per
+// image, when tmapS1 != nullptr; + the solve's scalar set-up, `setup`) in one launch
 void launch_time_prep(const Dims& d, const float* w1, const float* w2, float* tmap1, float* tmap2, float* wtime1, float* wtime2,
-                      float* const* zero, const size_t* zero_n, int nzero /*<= 8: regions to zero-fill*/, hipStream_t s);
+                      float* const* zero, const size_t* zero_n, int nzero /*<= 12: regions to zero-fill*/, hipStream_t s,
+                      float* tmapS1 = nullptr, float* tmapS2 = nullptr, int Q = 1, const SolveSetup* setup = nullptr);
 void launch_theta_to_torch(const Dims& d, const float* theta_int, float* flat, hipStream_t s);
 
 // pointwise / reductions
@@ -334,6 +365,9 @@ struct CommitArgs {
   const float* k[3][7];    // aug only: all stage derivatives (dense output at the interval's end)
   size_t n[3];
   int interp_final;        // aug: when the interval's end is passed, y[s] <- dense output at targets[0] (in place)
+  // deferred completion, the LAST step enqueued (nullable): the record a k_export_record launch behind this one would leave --
+  // one thread, in front of every early return; it reads the controller's record only, which this kernel never writes
+  node_step_record* rec; float* miss_flag; int expect_steps;
 };
 void launch_commit(const CommitArgs& a, hipStream_t s);
 void launch_set_interval(Ctrl* ctrl, double t, double dt, hipStream_t s);   // new interval: t, dt, done = 0, counters of the interval

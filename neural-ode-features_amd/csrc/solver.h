@@ -35,6 +35,10 @@ struct StepIO {
   int n_forced = 0;        // > 0: replay mode
   int log_cap = 0;         // > 0: dt log wanted
   float* y_out = nullptr;  // forward: [n_targets][N][C][H][W], slot j <-> target j
+  // deferred completion, set for the LAST step enqueued only: its commit launch leaves the caller's record (CommitArgs::rec)
+  node_step_record* rec = nullptr;
+  float* miss_flag = nullptr;
+  int expect_steps = 0;
 };
 
 // the evaluation that follows the one being enqueued: its combine may ride in this one's last pass
@@ -96,6 +100,19 @@ struct Solver {
   // the weight gradients of an augmented evaluation in the F(4x4,3x3) domain (k_w4_wgrad): needs the forward convs'
   // row operands alive behind the data-gradient convs, so they get buffers of their own
   bool w4_wgrad_on() const { return w4 && aug && p.W4dU != nullptr; }
+  // ---- the theta finalize of an augmented evaluation that is followed by another of the same step (s = 1..4 of enqueue_step's
+  // loop, the stage derivatives k3..k6: s = 0 has no finalize -- NODE_TUNE_SKIP_K2_THETA -- and s = 5 has no `next`, four per step)
+  // is not launched: it waits here and rides in the next evaluation's P2 launch (k_w4s_pass_rider).
+  // No hazard, checked against eval_w4: the finalize of evaluation i reads W4dU (or wpart), gpart[0..2], spart[0..1], wtime and
+  // sred.  Between PB1C(i) and P2(i+1) only gemm0(i+1) runs, which reads V / U and writes M.  P2(i+1) writes W4Va[1] (or W4V),
+  // xh2, r2 (and act2 without the F(4x4,3x3) weight gradient).  The first launches that write what the finalize reads are
+  // P3B3(i+1) (gpart[2], spart[1]), PB2(i+1) (gpart[1], spart[0]), the weight gradient (W4dU / wpart) and PB1(i+1) (gpart[0]):
+  // all of them behind the kernel boundary after P2(i+1).  What it writes -- KT[k], and ctrl->ts_k[k] from its last workgroup --
+  // nothing reads before the step's k_error_norm / k_step_controller; P2 reads ctrl->done, t, dt (h0), other words of the record.
+  // A waiting finalize never survives the end of enqueue_step. ----
+  bool theta_rider = true;          // NODE_TUNE_THETA_RIDER (default 1; 0: every finalize is its own launch), read in prepare()
+  bool tf_waiting = false;
+  ThetaFinalizeArgs tf_wait;
 
   void to_state(const float* nchw, float* dst) {    // NCHW -> the solve's internal state layout
     if (w4) launch_w4s_from_nchw(nchw, dst, d.N, d.C, d.w4q, st);
@@ -120,7 +137,8 @@ struct Solver {
   int check_launch(const char* what);
 
   // ---- set-up launches of a solve: filter packing, border maps, the solve's zero fills ----
-  int prepare();
+  // `setup`: the caller's scalar set-up of the solve and one more zero fill, carried by the preparation launch (SolveSetup)
+  int prepare(const SolveSetup* setup = nullptr);
 
   // ---- one evaluation of the dynamics ----
   // f(t, y_i) with y_i = cy; writes k_out = tsign * f  (and y_i to y_out if asked)
@@ -154,7 +172,8 @@ struct Solver {
   void w4_tail_combine(W4sArgs& a, const Comb& cy, float* y_out, bool train, int set, int self);
   // launch one pass; under node_profile_begin() with HIP events around it and its algorithmic bytes (every tensor it
   // must read or write, once) in the record
-  void w4_pass(int head, int tail, const W4sArgs& a);
+  // `rider` (P2 only): the waiting theta finalize that this launch carries
+  void w4_pass(int head, int tail, const W4sArgs& a, const ThetaFinalizeArgs* rider = nullptr);
   // One dynamics evaluation (ca == nullptr) or one augmented evaluation on the F(4x4,3x3) pipeline.  `next`: the
   // evaluation that follows takes its conv input from this one's last pass (v_ready).
   int eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_out, bool train, const Comb* ca, float* a_out, float* kA_out,

@@ -141,7 +141,7 @@ int Solver::check_launch(const char* what) {
   return NODE_OK;
 }
 
-int Solver::prepare() {
+int Solver::prepare(const SolveSetup* setup) {
   auto pack = d.wino == 2 ? launch_pack_weights_w2 : d.wino ? launch_pack_weights_w : launch_pack_weights;
   // zero fills of the solve, folded into the preparation launch below: the stage-2 parameter derivative (read with
   // weight zero by the error norm / dense output, never written by dopri5 steps -- the initial-step probe does
@@ -178,9 +178,13 @@ int Solver::prepare() {
     g_ready = false;
     if (w4_f16) { zr[nz] = reinterpret_cast<float*>(p.w4sc); zn[nz++] = sizeof(W4Scales) / sizeof(float); }
   }
+  if (setup != nullptr && setup->zero != nullptr) {
+    if (nz >= 12) return fail(NODE_ERR_ARG, "prepare(): more zero fills than the preparation launch carries");
+    zr[nz] = setup->zero; zn[nz++] = setup->zero_n;
+  }
   // (first: it carries the solve's zero fills, among them the scratch words of k_w4_scales)
   launch_time_prep(d, prm.conv1_w, prm.conv2_w, p.tmap[0], p.tmap[1], aug ? p.wtime[0] : nullptr, aug ? p.wtime[1] : nullptr, zr, zn,
-                   nz, st);
+                   nz, st, w4 ? p.tmapS[0] : nullptr, w4 ? p.tmapS[1] : nullptr, d.w4q, setup);
   if (w4) {
     W4PackJobs jobs;
     memset(&jobs, 0, sizeof(jobs));
@@ -212,7 +216,6 @@ int Solver::prepare() {
       pack(d, prm.conv2_w, p.wd[1], 1, st);
     }
   }
-  if (w4) launch_w4s_tmap(p.tmap[0], p.tmap[1], p.tmapS[0], p.tmapS[1], d.C, d.w4q, st);
   if (w4 && aug && d.N * d.w4q != d.N8 && p.W4dU != nullptr) {
     // the weight gradient SUMS over the GEMM rows: the rows of the padding samples (never written by a pass) must be zero
     for (int i = 0; i < 2; ++i) {
@@ -223,6 +226,8 @@ int Solver::prepare() {
   }
   v_ready = false;
   cur = 0;
+  theta_rider = env_int("NODE_TUNE_THETA_RIDER", 1) != 0;     // (read per solve: tests switch it inside one process)
+  tf_waiting = false;
   return check_launch("prepare");
 }
 
@@ -268,7 +273,7 @@ void Solver::w4_tail_combine(W4sArgs& a, const Comb& cy, float* y_out, bool trai
   if (f16_now()) a.v_exp = &p.w4sc->e[W4_E_V1];
 }
 
-void Solver::w4_pass(int head, int tail, const W4sArgs& a) {
+void Solver::w4_pass(int head, int tail, const W4sArgs& a, const ThetaFinalizeArgs* rider) {
   double bytes = 0.0;
   if (g_prof.on) {
     const double state = (double)d.numel * sizeof(float), comp = 36.0 * 4.0 * d.N * d.w4q * d.C * sizeof(float);
@@ -284,10 +289,16 @@ void Solver::w4_pass(int head, int tail, const W4sArgs& a) {
     }
     if (a.V) bytes += comp;
     bytes += tensors * state;
+    if (rider != nullptr) {     // what the finalize reads (weight-gradient partials, GroupNorm / masked-sum partials) and writes (theta)
+      const double cc = (double)d.C * d.C * sizeof(float), rows = (double)d.N * d.w4q;
+      bytes += (rider->dU != nullptr ? 2.0 * W4_COMPS : 2.0 * 9.0 * d.nsplit) * cc;
+      bytes += rows * (3.0 * 2.0 + 2.0 * 9.0) * d.C * sizeof(float) + (double)d.P * sizeof(float);
+    }
   }
   const int cls = head == 0 ? 3 : head == 1 ? 4 + tail : 7 + tail;
   ProfScope ps(cls, bytes, st);
-  launch_w4s_pass(head, tail, a, st);
+  if (rider != nullptr) launch_w4s_p2_rider(a, *rider, d, st);
+  else launch_w4s_pass(head, tail, a, st);
 }
 
 int Solver::eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_out, bool train, const Comb* ca, float* a_out,
@@ -311,7 +322,8 @@ int Solver::eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_
     if (train) { a.h.out_nhwc = wg4 ? nullptr : p.act2; a.h.xhat_s = p.xh2; a.h.rstd = p.r2; }
     a.V = wg4 ? p.W4Va[1] : p.W4V;
     if (f16_now()) a.v_exp = &p.w4sc->e[W4_E_V2];
-    w4_pass(1, 0, a);
+    w4_pass(1, 0, a, tf_waiting ? &tf_wait : nullptr);     // (with the finalize of the evaluation in front, if it waits: solver.h)
+    tf_waiting = false;
   }
   w4_gemm(1, wg4 ? p.W4Va[1] : nullptr);
   W4sArgs a3 = w4_args();
@@ -397,7 +409,12 @@ int Solver::eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_
   tf.wtime[0] = p.wtime[0]; tf.wtime[1] = p.wtime[1]; tf.sred = p.sred;
   tf.et = et; tf.osign = et.tsign; tf.theta_out = kT_out;
   tf.ctrl = p.ctrl; tf.kidx = kidx; tf.write_scalar = kidx >= 0 ? 1 : 0; tf.vjp_t_out = vjp_t_out;
-  launch_theta_finalize(d, tf, st);
+  if (theta_rider && next != nullptr && w4s_rider_fits(d.cpg, d.w4q)) {   // another evaluation of this step follows: its P2 launch carries it
+    tf_wait = tf;
+    tf_waiting = true;
+  } else {
+    launch_theta_finalize(d, tf, st);
+  }
   return check_launch("augmented dynamics (F(4x4,3x3))");
 }
 
@@ -572,9 +589,13 @@ int Solver::enqueue_step(const StepIO& io) {
   for (int s = 0; s < 6; ++s) {
     const int rc = eval_sys(s + 1, DP_BETA[s], s + 1, SC_DT, et_stage(DP_ALPHA[s]), s == 5, !(skip_k2 && s == 0),
                             s < 5 ? DP_BETA[s + 1] : nullptr, s + 2, s + 1 == 5);
-    if (rc != NODE_OK) { count_nfe = was_counting; return rc; }
+    if (rc != NODE_OK) { count_nfe = was_counting; tf_waiting = false; return rc; }
   }
   count_nfe = was_counting;
+  if (tf_waiting) {     // (the last stage has no `next`: nothing can wait here)
+    tf_waiting = false;
+    return fail(NODE_ERR_HIP, "a theta finalize was left waiting at the end of a dopri5 step");
+  }
   const int nseg = aug ? 3 : 1;
   ErrSeg es[3];
   es[0].y0 = p.Y; es[0].y1 = p.Y1; es[0].n = d.numel; es[0].compute_y1 = 0;
@@ -620,6 +641,7 @@ int Solver::enqueue_step(const StepIO& io) {
     cm.y[2] = p.TH; cm.y1[2] = p.TH1; cm.k0[2] = p.KT[0]; cm.k6[2] = p.KT[6]; cm.n[2] = d.P;
     for (int j = 0; j < 7; ++j) { cm.k[1][j] = p.KA[j]; cm.k[2][j] = p.KT[j]; }
   }
+  cm.rec = io.rec; cm.miss_flag = io.miss_flag; cm.expect_steps = io.expect_steps;
   launch_commit(cm, st);
   return check_launch("dopri5 step");
 }

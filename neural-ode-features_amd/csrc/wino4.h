@@ -141,7 +141,7 @@ __host__ __device__ inline size_t w4_u_elems(int C) { return (size_t)W4_COMPS * 
 struct W4sHead {          // the conv result in front of this pass
   const float* M;         // component products [N][C/32][36][4][32]
   const float* bias;      // forward: conv bias [C]
-  const float* tmapS;     // forward: border-aware time-channel map in the W4S blocking (launch_w4s_tmap)
+  const float* tmapS;     // forward: border-aware time-channel map in the W4S blocking (k_time_prep)
   EvalTime et;            // forward: time of the evaluation (tmap multiplier)
   const float* gamma;     // GroupNorm weight of this pass [C]
   const float* beta;      // forward: GroupNorm bias; backward: bias of the layer's ReLU mask fma(xhat, gamma, beta) > 0
@@ -185,9 +185,20 @@ struct W4sArgs {
 };
 // head: 0 none / 1 forward / 2 backward; tail: 0 none / 1 stage combine + GroupNorm-1 + ReLU / 2 adjoint combine + GroupNorm-3 backward
 void launch_w4s_pass(int head, int tail, const W4sArgs& a, hipStream_t s);
+// P2 (head 1, tail 0) with the theta finalize of the evaluation in front as the first workgroups of its grid (k_w4s_pass_rider):
+// what travels with W4sArgs, by value
+struct W4sRider {
+  ThetaFinalizeArgs tf;
+  Dims d;
+  int blocks;             // workgroups of the finalize (theta_finalize_blocks), in front of the pass's own
+};
+bool w4s_rider_fits(int cpg, int Q);     // the pass's workgroups have 128 or 256 threads (not Q = 4 with cpg = 32)
+void launch_w4s_p2_rider(const W4sArgs& a, const ThetaFinalizeArgs& tf, const Dims& d, hipStream_t s);
 void launch_w4s_from_nchw(const float* src_nchw, float* dst_w4s, int N, int C, int Q, hipStream_t s);
+// one launch for up to two NCHW -> W4S conversions of the same shape; copy[i][0..1] (nullable): NCHW tensors that get job i's source too
+struct W4sLayoutJobs { const float* src[2]; float* dst[2]; float* copy[2][2]; int njobs; };
+void launch_w4s_from_nchw_jobs(const W4sLayoutJobs& j, int N, int C, int Q, hipStream_t s);
 void launch_w4s_to_nchw(const float* src_w4s, float* dst_nchw, int N, int C, int Q, hipStream_t s);
-void launch_w4s_tmap(const float* tmap0, const float* tmap1, float* out0, float* out1, int C, int Q, hipStream_t s);
 void launch_w4s_emit_outputs(const Dims& d, const EmitArgs& a, hipStream_t s);
 
 // F(4x4,3x3)-domain weight gradient of both conv layers (k_w4_wgrad, kernels_w4_wgrad.hip).
