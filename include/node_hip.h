@@ -550,6 +550,50 @@ int node_trunk_fwd(const node_trunk_shape* shape, const node_trunk_block* blocks
 int node_trunk_bwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* grad_out,
                    const node_trunk_block_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
 
+/* The dynamics of an ODE block with norm = 'batch' -- model.py:326-348 with model.py:274:
+ *     f(t, x) = norm3(conv2(t, relu(norm2(conv1(t, relu(norm1(x)))))))
+ * norm = nn.BatchNorm2d(channels, track_running_stats=False): statistics of the BATCH (mean and biased variance per channel
+ * over n h w values) in training and evaluation alike, affine, no running buffers; conv = ConcatConv2d (model.py:313-323): a
+ * 3x3 / stride 1 / padding 1 convolution with bias over [t * 1, x], filter [channels, channels + 1, 3, 3], input channel 0 =
+ * the time plane.  One evaluation and its vector-Jacobian product, on the stem's kernels: gather GEMMs on the bf16 matrix
+ * pipe at fp32 accuracy for the x part of the filters, the time channel as the additive term t * (sum of the time taps inside
+ * the image) that the BatchNorm passes add while they read the convolution's output, BatchNorm statistics in two stages
+ * (centred second moments per chunk of rows, combined by Chan's formula in a fixed order).
+ * t: a DEVICE scalar (the calls never read it on the host).  x, out, grad_out, d_x: [n, channels, h, w] NCHW fp32.
+ *   channels: a multiple of 64 in [64, 4096] (192 is fine: BatchNorm has no groups); any n >= 1; h, w >= 3; tensors under
+ *   2^31 elements.  Anything else: NODE_ERR_UNSUPPORTED with a message, and the workspace-size call returns 0.
+ * The backward needs the workspace exactly as the forward left it with keep_for_backward = 1 (one workspace per forward in
+ * flight).  It writes (does not accumulate) what is asked for: grads (NULL: no parameter gradient wanted; otherwise all
+ * ten), d_x (NULL: not wanted), d_t (NULL: not wanted; a device scalar).  The gradient of a convolution's bias in front of a
+ * BatchNorm is zero identically: conv1_b / conv2_b receive the computed sum, rounding noise around zero.  No floating-point
+ * atomics: every sum runs in a fixed order, so results are bit-reproducible run to run.  The calls never synchronise,
+ * allocate device memory or read back; NULL and misaligned arguments are rejected before any launch. */
+typedef struct node_bnfunc_shape {
+  int32_t n, channels, h, w;
+  float eps;
+} node_bnfunc_shape;
+typedef struct node_bnfunc_params {      /* ODEfunc.named_parameters() order */
+  const float* norm1_w; /* [C] */
+  const float* norm1_b; /* [C] */
+  const float* conv1_w; /* conv1._layer.weight [C, C + 1, 3, 3] */
+  const float* conv1_b; /* conv1._layer.bias   [C] */
+  const float* norm2_w;
+  const float* norm2_b;
+  const float* conv2_w;
+  const float* conv2_b;
+  const float* norm3_w;
+  const float* norm3_b;
+} node_bnfunc_params;
+typedef struct node_bnfunc_grads {       /* same order and shapes; device pointers */
+  float* norm1_w; float* norm1_b; float* conv1_w; float* conv1_b; float* norm2_w; float* norm2_b;
+  float* conv2_w; float* conv2_b; float* norm3_w; float* norm3_b;
+} node_bnfunc_grads;
+size_t node_bnfunc_workspace_bytes(const node_bnfunc_shape* shape, int keep_for_backward);
+int node_bnfunc_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* params, const float* t, const float* x, float* out,
+                    int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_bnfunc_bwd(const node_bnfunc_shape* shape, const node_bnfunc_params* params, const float* t, const float* grad_out,
+                    const node_bnfunc_grads* grads, float* d_x, float* d_t, void* ws, size_t ws_bytes, void* stream);
+
 /* The hand-off between the two solves of the `ode2` stem -- model.py:199-223 (`ODEDownsample2`: `conv2(norm(x))`):
  *     y = conv(relu(norm(x))),   norm = nn.GroupNorm(min(32, cin), cin),   conv = nn.Conv2d(cin, cout, 4, 2, 1) with bias
  * on the stem's kernels: the GroupNorm + ReLU pass writes the exact bf16 triples the gather GEMM reads, the 16 taps of the

@@ -51,6 +51,7 @@ EXPORTS = [
     'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd', 'node_convstem_bwd_dx',
     'node_ministem_workspace_bytes', 'node_ministem_fwd', 'node_ministem_bwd',
     'node_pool_fwd', 'node_pool_bwd',
+    'node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd',
 ]
 
 
@@ -150,6 +151,17 @@ class NodeTrunkShape(C.Structure):
 
 class NodeTrunkBlock(C.Structure):          # node_trunk_block and node_trunk_block_grads share this layout
     _fields_ = [(k, C.c_void_p) for k in TRUNK_BLOCK_FIELDS]
+
+
+BNFUNC_PARAM_FIELDS = ('norm1_w', 'norm1_b', 'conv1_w', 'conv1_b', 'norm2_w', 'norm2_b', 'conv2_w', 'conv2_b', 'norm3_w', 'norm3_b')
+
+
+class NodeBnfuncShape(C.Structure):
+    _fields_ = [('n', C.c_int32), ('channels', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('eps', C.c_float)]
+
+
+class NodeBnfuncParams(C.Structure):        # node_bnfunc_params and node_bnfunc_grads share this layout
+    _fields_ = [(k, C.c_void_p) for k in BNFUNC_PARAM_FIELDS]
 
 
 DOWNCONV_PARAM_FIELDS = ('gn_w', 'gn_b', 'conv_w', 'conv_b')
@@ -406,6 +418,12 @@ def load():
     lib.node_trunk_workspace_bytes.argtypes = [P(NodeTrunkShape), i32]
     lib.node_trunk_fwd.restype = i32
     lib.node_trunk_fwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, vp, vp, i32, vp, sz, vp]
+    lib.node_bnfunc_workspace_bytes.restype = sz
+    lib.node_bnfunc_workspace_bytes.argtypes = [P(NodeBnfuncShape), i32]
+    lib.node_bnfunc_fwd.restype = i32
+    lib.node_bnfunc_fwd.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, vp, i32, vp, sz, vp]
+    lib.node_bnfunc_bwd.restype = i32
+    lib.node_bnfunc_bwd.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, P(NodeBnfuncParams), vp, vp, vp, sz, vp]
     lib.node_trunk_bwd.restype = i32
     lib.node_trunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
     lib.node_downconv_workspace_bytes.restype = sz

@@ -1,0 +1,79 @@
+// BatchNorm (batch statistics, no running buffers: nn.BatchNorm2d(C, track_running_stats=False), model.py:274) over an NHWC
+// tensor [rows = N H W][C] for the stem's kernel family, and the time channel of ConcatConv2d (model.py:313-323) for its
+// gather GEMMs: internal declarations shared by kernels_batchnorm.hip (kernels + launchers) and bnfunc_api.hip (the C ABI).
+#pragma once
+#include "stem.h"
+
+namespace node {
+
+// A BatchNorm pass works on (chunk of rows) x (64 channels) per workgroup; statistics are taken in two stages: every
+// workgroup writes its chunk's partials, every CONSUMER combines the partials of its 64 channels in one fixed order.
+//
+// The normalised tensor is  u = h + t * T[class(pixel)][c]  when T is given: h is what the gather GEMM wrote (filter
+// w[:, 1:], bias in its epilogue), and the time channel of ConcatConv2d -- a constant plane t in front of a zero-padded
+// 3x3 filter -- is the additive term t * (sum of w[co, 0, ky, kx] over the taps inside the image): nine values per output
+// channel, class = 3 * (top, middle, bottom row) + (left, middle, right column).  Every pass that reads h adds it on the
+// fly, so the term costs no pass over the tensor.  t is a DEVICE scalar.
+struct SBnArgs {
+  const float* h;          // fp32 NHWC [rows][C]
+  const float* T;          // nullable [9][C]
+  const float* t;          // device scalar (read only with T)
+  const float* gamma;
+  const float* beta;
+  float* part;             // forward [nchunk][2][C]: (chunk mean, centred second moment)
+  float* stats;            // [2][C]: batch mean, 1 / sqrt(biased variance + eps): written by the apply pass, read by the backward
+  int rows, C, H, W;
+  int chunk_rows, nchunk;  // chunk_rows % 32 == 0
+  int relu;
+  float eps;
+  // apply: y = [relu](xhat gamma + beta) as triples and / or fp32 NHWC
+  bf16_t* a3;
+  size_t a_plane;
+  float* y;
+  // backward: da = dL/dy
+  const float* da;
+  double* gpart;           // [nchunk][2][C]: (sum dy, sum dy xhat) of the chunk, fp64 (kernels_batchnorm.hip says why)
+  float* dh;               // nullable fp32 NHWC gradient of u
+  bf16_t* dh3;             // nullable triples of the same
+  size_t dh_plane;
+  float* dgamma;           // nullable [C] (written by the chunk-0 workgroups of the dx pass)
+  float* dbeta;
+  float* clsp;             // nullable [nchunk][9][C]: per-chunk sums of the gradient of u over the pixels of each class
+  double* dtp;             // with clsp: [nchunk][C / 64], the workgroup's share of sum du * (T - T[interior]) (fp64: the sum cancels heavily)
+};
+// rows per chunk for a tensor of `rows` x C: <= 128 chunks, enough (chunk, channel block) pairs to cover the device
+int bn_chunk_rows(int rows, int C);
+void launch_bn_stats(const SBnArgs& a, hipStream_t s);
+void launch_bn_apply(const SBnArgs& a, hipStream_t s);
+void launch_bn_bwd_stats(const SBnArgs& a, hipStream_t s);
+void launch_bn_bwd_dx(const SBnArgs& a, hipStream_t s);
+
+// once per forward: the x part w[:, 1:] of both ConcatConv2d filters [C][C + 1][3][3] -> triples in both operand layouts
+// (as k_stem_prep does for a contiguous filter), the time tables T[9][C], the zero rows of `nzero` triples tensors
+struct SBnPrepArgs {
+  const float* w[2];
+  bf16_t* wf[2];
+  bf16_t* wd[2];
+  float* T[2];
+  int C;
+  bf16_t* zero[3]; size_t zero_plane[3]; int nzero;
+};
+void launch_bn_prep(const SBnPrepArgs& a, hipStream_t s);
+
+// once per backward: split-K slabs [ns][9][C][C] -> dW[:, 1:] of the [C][C + 1][3][3] filters; the class sums -> dW[:, 0],
+// the bias gradients, and d_t = sum over both convolutions of du * T (fixed order; device scalar)
+struct SBnReduceArgs {
+  const float* slab0; const float* slab1;
+  int ns0, ns1;
+  float* dw0; float* dw1;
+  float* db0; float* db1;
+  const float* clsp0; const float* clsp1;
+  const double* dtp0; const double* dtp1;
+  int nchunk, C;
+  const float* t;
+  float* d_t;              // nullable
+  int want_params;
+};
+void launch_bn_reduce(const SBnReduceArgs& a, hipStream_t s);
+
+}  // namespace node

@@ -25,7 +25,8 @@ from . import integrate
 
 def normalization(norm: str = 'group'):
     """model.py:268-281.  'group' dynamics run on the fused kernels; 'batch' (model.py:274: BatchNorm2d without running
-    statistics -- it couples the samples of a batch, so no fused kernel takes it) runs the generic solver (generic.py)."""
+    statistics -- it couples the samples of a batch, so the fused ODE block does not take it) runs the generic solver
+    (generic.py), whose function evaluations are one HIP node each (bnfunc.py)."""
     if norm == 'group':
         return lambda dim: nn.GroupNorm(min(32, dim), dim)
     if norm == 'batch':
@@ -48,7 +49,14 @@ class ConcatConv2d(nn.Module):
 
 
 class ODEfunc(nn.Module):
-    """f(t, x) = GN3(conv2(t, relu(GN2(conv1(t, relu(GN1(x)))))))."""
+    """f(t, x) = GN3(conv2(t, relu(GN2(conv1(t, relu(GN1(x))))))).
+
+    With `norm='batch'` a call on a HIP fp32 batch of a shape the library takes (bnfunc.plan) is ONE autograd node on the
+    package's kernels (bnfunc._BatchOdeFn: forward, and a backward that returns the gradients of t, x and the parameters);
+    `ODEfunc.fused_batch = False` switches that off for every instance (A/B measurements, tests).  Every other call runs
+    the module operations below."""
+
+    fused_batch = True
 
     def __init__(self, dim, norm='group'):
         super().__init__()
@@ -63,6 +71,11 @@ class ODEfunc(nn.Module):
 
     def forward(self, t, x):
         self.nfe += 1
+        if self.fused_batch and isinstance(self.norm1, nn.BatchNorm2d):
+            from . import bnfunc
+            taken = bnfunc.plan(self, t, x)
+            if taken is not None:
+                return bnfunc.evaluate(t, x, *taken)
         h = F.relu(self.norm1(x))
         h = F.relu(self.norm2(self.conv1(t, h)))
         return self.norm3(self.conv2(t, h))

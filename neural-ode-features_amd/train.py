@@ -221,7 +221,7 @@ def build_parser():
         (('-m', '--model'), dict(type=str, choices=('resnet', 'odenet'), default='odenet')),
         (('--dataset',), dict(type=str, choices=tuple(SHAPES), default='mnist')),
         (('-d', '--downsample'), dict(type=str, choices=stems, default='residual')),
-        (('-n', '--norm'), dict(type=str, choices=('group',), default='group')),
+        (('-n', '--norm'), dict(type=str, choices=('group', 'batch'), default='group')),
         (('-f', '--filters'), dict(type=int, default=64)),
         (('--dropout',), dict(type=float, default=0)),
         (('-e', '--epochs'), dict(type=int, default=100)),
@@ -258,6 +258,8 @@ def default_run_dir(args):
         name = 'resnet_%s_f%d' % (args.downsample, args.filters)
     else:
         name = 'odenet_%s_f%d_%s_tol%g%s' % (args.downsample, args.filters, args.method, args.tol, '_adjoint' if args.adjoint else '')
+    if getattr(args, 'norm', 'group') == 'batch':        # (only then: the names of group-norm runs stay what they were)
+        name += '_batch'
     return os.path.join('runs_' + args.dataset, name)
 
 
@@ -272,6 +274,12 @@ def main(argv=None):
             # a ResNet step has no solve, so there is no read-back to defer and no step count that could miss
             raise SystemExit('--deferred defers the completion of ODE solves: --model resnet has none (its steps never wait '
                              'for the device); run it without --deferred')
+
+    if args.deferred and args.norm == 'batch' and args.model == 'odenet':
+        # batch-norm dynamics are solved by the generic solver (generic.py), which reads its step controller back once per solve:
+        # there is no completion left to defer, and no device flag a missed step count could raise
+        raise SystemExit('--deferred defers the completion read-back of the fused solves: --norm batch dynamics run the generic '
+                         'solver, which reads its controller back in every solve; run it without --deferred')
 
     torch.manual_seed(args.seed)
     if not torch.cuda.is_available():
