@@ -594,6 +594,39 @@ int node_bnfunc_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* pa
 int node_bnfunc_bwd(const node_bnfunc_shape* shape, const node_bnfunc_params* params, const float* t, const float* grad_out,
                     const node_bnfunc_grads* grads, float* d_x, float* d_t, void* ws, size_t ws_bytes, void* stream);
 
+/* A whole SOLVE of these dynamics, forward and continuous adjoint: what the generic solver does around node_bnfunc_fwd / _bwd
+ * (stage states, Hairer's initial step, error norms, accept / reject, dense output, FSAL: the node_flat_* kernels), driven from
+ * inside the library.  The state stays in the BatchNorm kernels' NHWC layout from the first stage to the last (NCHW at the
+ * boundary only: y0, y_out, y_traj, grad_out, grad_y0 are [.., n, channels, h, w]), the parameters are prepared once per solve,
+ * and every evaluation writes tsign * f and tsign * vjp(-a) straight into the stage-derivative slots.
+ *   method: NODE_METHOD_DOPRI5, or NODE_METHOD_RK4 (3/8 rule, one step per interval of t_pts, times rounded to fp32).
+ *   t_pts: HOST array of n_t >= 2 times, strictly increasing or strictly decreasing (NODE_ERR_ARG otherwise).
+ *   Shapes: those of node_bnfunc_fwd, and the n_t slices of a call together under 2^31 elements (n_t <= 1024); the workspace
+ *   query returns 0 with a message for anything else.
+ *   y_out: [n_t] slices, y_out[0] = y0 bit for bit.  y_traj: what node_bnsolve_fwd returned.  grad_out: [n_t] slices, or ONE
+ *   slice (the last one's) with opts->grad_last_only.  grad_params: NULL (not wanted) or all ten; written, not accumulated.
+ * The calls read the step controller back (they synchronise the stream) once per `steps_hint` / two steps until it reports the
+ * interval done; the host takes no step decision.  Steps enqueued past the end of an interval run on discarded states, so no
+ * result depends on the hint.  A controller status -- NODE_ERR_MAX_STEPS, NODE_ERR_NONFINITE, NODE_ERR_DT_UNDERFLOW -- is the
+ * return code, with stats->status set.  stats->nfe counts what the generic solver leaves in func.nfe for the same step history:
+ * forward 2 + 6 steps tried (rk4: 4 per interval); adjoint, per interval, one f(t_i, y_i) plus 2 + 6 steps tried (rk4: 4).
+ * The caller owns every byte: the workspace holds the evaluation's plan, the flat segments (y, y1, a stage state and seven stage
+ * derivatives each; y alone forward, y / adj_y / adj_params in the adjoint, adj_t in the controller), the NHWC slices and the
+ * controller.  No floating-point atomics: the same bits on every run. */
+typedef struct node_bnsolve_opts {
+  int32_t max_num_steps;    /* <= 0: 2^31 - 1; steps tried per interval */
+  int32_t steps_hint;       /* dopri5 steps enqueued before the first read-back (<= 0: 1); later rounds enqueue 2 */
+  int32_t grad_last_only;   /* node_bnsolve_adjoint: as in node_solve_opts */
+} node_bnsolve_opts;
+size_t node_bnsolve_workspace_bytes(const node_bnfunc_shape* shape, int method, int adjoint, int n_t);   /* 0: refused, with a message */
+int node_bnsolve_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* params, const float* y0, const float* t_pts, int n_t,
+                     float rtol, float atol, int method, const node_bnsolve_opts* opts, float* y_out, node_stats* stats,
+                     void* ws, size_t ws_bytes, void* stream);
+int node_bnsolve_adjoint(const node_bnfunc_shape* shape, const node_bnfunc_params* params, const float* y_traj, const float* grad_out,
+                         const float* t_pts, int n_t, float rtol, float atol, int method, const node_bnsolve_opts* opts,
+                         float* grad_y0, const node_bnfunc_grads* grad_params, node_stats* stats, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* The hand-off between the two solves of the `ode2` stem -- model.py:199-223 (`ODEDownsample2`: `conv2(norm(x))`):
  *     y = conv(relu(norm(x))),   norm = nn.GroupNorm(min(32, cin), cin),   conv = nn.Conv2d(cin, cout, 4, 2, 1) with bias
  * on the stem's kernels: the GroupNorm + ReLU pass writes the exact bf16 triples the gather GEMM reads, the 16 taps of the

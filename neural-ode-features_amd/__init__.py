@@ -10,7 +10,7 @@ reference's `model.py` runs unchanged on top of the HIP library:
 from .integrate import odeint, odeint_adjoint, odefunc_forward, odefunc_vjp  # noqa: F401
 from .modules import ConcatConv2d, ODEBlock, ODEfunc, normalization  # noqa: F401
 from .odenet import FCClassifier, ODEDownsample, ODEDownsample2, ODENet, ResBlock, StackedODENet  # noqa: F401
-from . import attack, augment, dp, finetune, graphs, optim, retrieval  # noqa: F401
+from . import attack, augment, bnsolve, dp, finetune, graphs, optim, retrieval  # noqa: F401
 from .augment import Augmenter, DeviceSplit, TransferTransform  # noqa: F401
 from .imgconv import ImageConv2d  # noqa: F401
 from .convstem import ConvStem  # noqa: F401

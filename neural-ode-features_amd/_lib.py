@@ -52,6 +52,7 @@ EXPORTS = [
     'node_ministem_workspace_bytes', 'node_ministem_fwd', 'node_ministem_bwd',
     'node_pool_fwd', 'node_pool_bwd',
     'node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd',
+    'node_bnsolve_workspace_bytes', 'node_bnsolve_fwd', 'node_bnsolve_adjoint',
 ]
 
 
@@ -162,6 +163,10 @@ class NodeBnfuncShape(C.Structure):
 
 class NodeBnfuncParams(C.Structure):        # node_bnfunc_params and node_bnfunc_grads share this layout
     _fields_ = [(k, C.c_void_p) for k in BNFUNC_PARAM_FIELDS]
+
+
+class NodeBnsolveOpts(C.Structure):
+    _fields_ = [('max_num_steps', C.c_int32), ('steps_hint', C.c_int32), ('grad_last_only', C.c_int32)]
 
 
 DOWNCONV_PARAM_FIELDS = ('gn_w', 'gn_b', 'conv_w', 'conv_b')
@@ -424,6 +429,14 @@ def load():
     lib.node_bnfunc_fwd.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, vp, i32, vp, sz, vp]
     lib.node_bnfunc_bwd.restype = i32
     lib.node_bnfunc_bwd.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, P(NodeBnfuncParams), vp, vp, vp, sz, vp]
+    lib.node_bnsolve_workspace_bytes.restype = sz
+    lib.node_bnsolve_workspace_bytes.argtypes = [P(NodeBnfuncShape), i32, i32, i32]
+    lib.node_bnsolve_fwd.restype = i32
+    lib.node_bnsolve_fwd.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, P(C.c_float), i32, f32, f32, i32, P(NodeBnsolveOpts),
+                                     vp, P(NodeStats), vp, sz, vp]
+    lib.node_bnsolve_adjoint.restype = i32
+    lib.node_bnsolve_adjoint.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, P(C.c_float), i32, f32, f32, i32,
+                                         P(NodeBnsolveOpts), vp, P(NodeBnfuncParams), P(NodeStats), vp, sz, vp]
     lib.node_trunk_bwd.restype = i32
     lib.node_trunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
     lib.node_downconv_workspace_bytes.restype = sz

@@ -40,6 +40,10 @@ struct SBnArgs {
   float* dbeta;
   float* clsp;             // nullable [nchunk][9][C]: per-chunk sums of the gradient of u over the pixels of each class
   double* dtp;             // with clsp: [nchunk][C / 64], the workgroup's share of sum du * (T - T[interior]) (fp64: the sum cancels heavily)
+  // multipliers of a solve's driver (bnsolve_api.hip); 1.0f, the default, is exact.  The gradient is linear in the cotangent, so a
+  // sign on `da` of the FIRST backward pass of an evaluation reaches every gradient it returns.
+  float out_scale = 1.0f;  // on the fp32 output `y` of the apply pass (the triples are not scaled)
+  float da_scale = 1.0f;   // on every read of `da` in the two backward passes
 };
 // rows per chunk for a tensor of `rows` x C: <= 128 chunks, enough (chunk, channel block) pairs to cover the device
 int bn_chunk_rows(int rows, int C);
@@ -75,5 +79,12 @@ struct SBnReduceArgs {
   int want_params;
 };
 void launch_bn_reduce(const SBnReduceArgs& a, hipStream_t s);
+
+// The small passes of a whole solve around these dynamics (bnsolve_api.hip); n % 4 == 0, 16-byte aligned tensors.
+// *out = sum a[i] * b[i]: two launches, fp64 partials [BN_DOT_BLOCKS] in a fixed order
+constexpr int BN_DOT_BLOCKS = 128;
+void launch_bn_dot(const float* a, const float* b, size_t n, double* part, float* out, hipStream_t s);
+void launch_bn_add(float* y, const float* x, size_t n, hipStream_t s);      // y += x
+void launch_bn_set_scalar(float* dst, float v, hipStream_t s);               // *dst = v (a device scalar: the time of an evaluation)
 
 }  // namespace node

@@ -12,32 +12,16 @@
 //            one reduction launch: slabs -> dW[:, 1:], class sums -> dW[:, 0] and db, d_t
 // The gradient of a convolution's bias in front of a BatchNorm is zero identically; what is returned is the computed sum
 // (rounding noise around zero), not a literal zero.  Nothing is accumulated with atomics: every sum runs in a fixed order.
-#include "host_common.h"
-#include "batchnorm.h"
-#include "stem_plan.h"
+//
+// The two entry points are preparation + layout launch + evaluation + layout launch; the evaluations themselves (bn_prepare,
+// bn_eval_fwd, bn_eval_bwd: NHWC to NHWC, bnfunc.h) are what a whole solve calls per stage without the other three
+// (bnsolve_api.hip).
+#include "bnfunc.h"
 #include <cstring>
 
-using namespace node;
+namespace node {
 
-namespace {
-
-struct BnPlan {
-  int N, C, H, W, R, cr, nchunk;
-  float eps;
-  Filt c1, c2;
-  float *T1, *T2;
-  float *xh, *h1, *h2, *y;
-  Trip a1, a2;
-  float *part, *stats1, *stats2, *stats3;
-  // backward
-  float *gf, *da, *clsp1, *clsp2;
-  double *gpart, *dtp1, *dtp2;
-  Trip dht;
-  Wg w1, w2;
-  size_t bytes;
-};
-
-BnPlan make_bn_plan(const node_bnfunc_shape* sh, bool keep, void* base) {
+BnPlan make_bn_plan(const node_bnfunc_shape* sh, bool keep, void* base, bool boundary) {
   BnPlan p;
   p.N = sh->n; p.C = sh->channels; p.H = sh->h; p.W = sh->w; p.eps = sh->eps;
   p.R = p.N * p.H * p.W;
@@ -50,12 +34,12 @@ BnPlan make_bn_plan(const node_bnfunc_shape* sh, bool keep, void* base) {
   p.c2 = take_filt(b, C, C, 9);
   p.T1 = b.take<float>((size_t)9 * C);
   p.T2 = b.take<float>((size_t)9 * C);
-  p.xh = b.take<float>(RC);
+  p.xh = boundary ? b.take<float>(RC) : nullptr;
   p.a1 = take_trip(b, p.R, C);
   p.h1 = b.take<float>(RC);
   p.a2 = take_trip(b, p.R, C);
   p.h2 = b.take<float>(RC);
-  p.y = b.take<float>(RC);
+  p.y = (boundary || keep) ? b.take<float>(RC) : nullptr;
   p.part = b.take<float>((size_t)p.nchunk * 2 * C);
   p.stats1 = b.take<float>((size_t)2 * C);
   p.stats2 = b.take<float>((size_t)2 * C);
@@ -91,7 +75,7 @@ int check_bn_shape(const node_bnfunc_shape* sh) {
   return NODE_OK;
 }
 
-int check_ten(const void* s, const char* what) {
+int check_bn_tensors(const void* s, const char* what) {
   if (!s) return fail(NODE_ERR_NULL, "%s is NULL", what);
   const void* const* pp = reinterpret_cast<const void* const*>(s);
   for (int k = 0; k < 10; ++k) {
@@ -100,18 +84,14 @@ int check_ten(const void* s, const char* what) {
   }
   return NODE_OK;
 }
-int check_ptr(const void* p, const char* what, bool required) {
-  if (!p) return required ? fail(NODE_ERR_NULL, "%s is NULL", what) : NODE_OK;
-  if (((uintptr_t)p) & 15) return fail(NODE_ERR_ARG, "%s must be 16-byte aligned", what);
-  return NODE_OK;
-}
-
+namespace {
 SBnArgs bn_args(const BnPlan& p, const float* h, const float* T, const float* t, const float* gamma, const float* beta, float* part,
                 float* stats, bool relu) {
   SBnArgs a;
   memset(&a, 0, sizeof(a));
   a.h = h; a.T = T; a.t = t; a.gamma = gamma; a.beta = beta; a.part = part; a.stats = stats;
   a.rows = p.R; a.C = p.C; a.H = p.H; a.W = p.W; a.chunk_rows = p.cr; a.nchunk = p.nchunk; a.relu = relu ? 1 : 0; a.eps = p.eps;
+  a.out_scale = 1.0f; a.da_scale = 1.0f;
   return a;
 }
 
@@ -122,47 +102,27 @@ SBnArgs bn_args(const BnPlan& p, const float* h, const float* T, const float* t,
 
 }  // namespace
 
-extern "C" {
-
-size_t node_bnfunc_workspace_bytes(const node_bnfunc_shape* shape, int keep_for_backward) {
-  if (check_bn_shape(shape) != NODE_OK) return 0;
-  return make_bn_plan(shape, keep_for_backward != 0, nullptr).bytes;
+int bn_prepare(const BnPlan& p, const node_bnfunc_params* prm, bool keep, hipStream_t st) {
+  SBnPrepArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.w[0] = prm->conv1_w; pa.wf[0] = p.c1.wf; pa.wd[0] = p.c1.wd; pa.T[0] = p.T1;
+  pa.w[1] = prm->conv2_w; pa.wf[1] = p.c2.wf; pa.wd[1] = p.c2.wd; pa.T[1] = p.T2;
+  pa.C = p.C;
+  const Trip* tz[3] = {&p.a1, &p.a2, &p.dht};
+  pa.nzero = keep ? 3 : 2;
+  for (int i = 0; i < pa.nzero; ++i) {
+    pa.zero[i] = tz[i]->p + (size_t)tz[i]->rows * p.C;
+    pa.zero_plane[i] = tz[i]->plane;
+  }
+  launch_bn_prep(pa, st);
+  return launch_ok("bn_prep");
 }
 
-int node_bnfunc_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* prm, const float* t, const float* x, float* out,
-                    int keep_for_backward, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_bn_shape(shape);
-  if (rc != NODE_OK) return rc;
-  if ((rc = check_ten(prm, "params")) != NODE_OK) return rc;
-  if (!t) return fail(NODE_ERR_NULL, "t is NULL (a device scalar)");
-  if (((uintptr_t)t) & 3) return fail(NODE_ERR_ARG, "t must be 4-byte aligned");
-  if ((rc = check_ptr(x, "x", true)) != NODE_OK || (rc = check_ptr(out, "out", true)) != NODE_OK) return rc;
-  if (!ws) return fail(NODE_ERR_NULL, "workspace is NULL");
-  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
-  const BnPlan p = make_bn_plan(shape, keep_for_backward != 0, ws);
-  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "bnfunc workspace too small: %zu < %zu", ws_bytes, p.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  const int N = p.N, C = p.C, H = p.H, W = p.W, HW = H * W;
-
-  {
-    SBnPrepArgs pa;
-    memset(&pa, 0, sizeof(pa));
-    pa.w[0] = prm->conv1_w; pa.wf[0] = p.c1.wf; pa.wd[0] = p.c1.wd; pa.T[0] = p.T1;
-    pa.w[1] = prm->conv2_w; pa.wf[1] = p.c2.wf; pa.wd[1] = p.c2.wd; pa.T[1] = p.T2;
-    pa.C = C;
-    const Trip* tz[3] = {&p.a1, &p.a2, &p.dht};
-    pa.nzero = keep_for_backward ? 3 : 2;
-    for (int i = 0; i < pa.nzero; ++i) {
-      pa.zero[i] = tz[i]->p + (size_t)tz[i]->rows * C;
-      pa.zero_plane[i] = tz[i]->plane;
-    }
-    launch_bn_prep(pa, st);
-    LAUNCHED("bn_prep");
-  }
-  launch_stem_from_nchw(x, p.xh, nullptr, 0, N, C, HW, st);
-  LAUNCHED("stem_from_nchw");
+int bn_eval_fwd(const BnPlan& p, const node_bnfunc_params* prm, const float* t, const float* x, float* out, float out_scale, hipStream_t st) {
+  int rc;
+  const int N = p.N, H = p.H, W = p.W;
   {   // a1 = relu(norm1(x))
-    SBnArgs a = bn_args(p, p.xh, nullptr, nullptr, prm->norm1_w, prm->norm1_b, p.part, p.stats1, true);
+    SBnArgs a = bn_args(p, x, nullptr, nullptr, prm->norm1_w, prm->norm1_b, p.part, p.stats1, true);
     launch_bn_stats(a, st);
     LAUNCHED("bn_stats");
     a.a3 = p.a1.p; a.a_plane = p.a1.plane;
@@ -189,40 +149,25 @@ int node_bnfunc_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* pr
     launch_stem_conv(c, st);
     LAUNCHED("stem_conv");
   }
-  {   // y = norm3(h2 + t T2)
+  {   // out = out_scale * norm3(h2 + t T2)
     SBnArgs a = bn_args(p, p.h2, p.T2, t, prm->norm3_w, prm->norm3_b, p.part, p.stats3, false);
     launch_bn_stats(a, st);
     LAUNCHED("bn_stats");
-    a.y = p.y;
+    a.y = out; a.out_scale = out_scale;
     launch_bn_apply(a, st);
     LAUNCHED("bn_apply");
   }
-  launch_stem_to_nchw(p.y, out, N, C, HW, st);
-  return launch_ok("node_bnfunc_fwd");
+  return NODE_OK;
 }
 
-int node_bnfunc_bwd(const node_bnfunc_shape* shape, const node_bnfunc_params* prm, const float* t, const float* grad_out,
-                    const node_bnfunc_grads* grads, float* d_x, float* d_t, void* ws, size_t ws_bytes, void* stream) {
-  int rc = check_bn_shape(shape);
-  if (rc != NODE_OK) return rc;
-  if ((rc = check_ten(prm, "params")) != NODE_OK) return rc;
-  if (grads && (rc = check_ten(grads, "grads")) != NODE_OK) return rc;
-  if (!t) return fail(NODE_ERR_NULL, "t is NULL (a device scalar)");
-  if ((((uintptr_t)t) & 3) || (((uintptr_t)d_t) & 3)) return fail(NODE_ERR_ARG, "t and d_t must be 4-byte aligned");
-  if ((rc = check_ptr(grad_out, "grad_out", true)) != NODE_OK || (rc = check_ptr(d_x, "d_x", false)) != NODE_OK) return rc;
-  if (!ws) return fail(NODE_ERR_NULL, "workspace is NULL");
-  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
-  const BnPlan p = make_bn_plan(shape, true, ws);
-  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "bnfunc workspace too small: %zu < %zu", ws_bytes, p.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  const int N = p.N, C = p.C, H = p.H, W = p.W, HW = H * W;
+int bn_eval_bwd(const BnPlan& p, const node_bnfunc_params* prm, const float* t, const float* x, const float* da, float da_scale,
+                const node_bnfunc_grads* grads, float* dx, bool want_dx, float* d_t, hipStream_t st) {
+  int rc;
+  const int N = p.N, C = p.C, H = p.H, W = p.W;
   const bool want_p = grads != nullptr, want_time = want_p || d_t != nullptr;
-
-  launch_stem_from_nchw(grad_out, p.gf, nullptr, 0, N, C, HW, st);
-  LAUNCHED("stem_from_nchw");
   {   // norm3: du2 -> triples
     SBnArgs a = bn_args(p, p.h2, p.T2, t, prm->norm3_w, prm->norm3_b, nullptr, p.stats3, false);
-    a.da = p.gf; a.gpart = p.gpart;
+    a.da = da; a.da_scale = da_scale; a.gpart = p.gpart;
     launch_bn_bwd_stats(a, st);
     LAUNCHED("bn_bwd_stats");
     a.dh3 = p.dht.p; a.dh_plane = p.dht.plane;
@@ -252,22 +197,18 @@ int node_bnfunc_bwd(const node_bnfunc_shape* shape, const node_bnfunc_params* pr
     launch_stem_wgrad(wgrad_args(p.dht, nullptr, p.a1, p.w1, N, H, W, H, W, C, C, 3, 1, 1), st);
     LAUNCHED("stem_wgrad");
   }
-  if (want_p || d_x) {
+  if (want_p || want_dx) {
     launch_stem_conv(conv_dgrad_args(p.dht, p.c1, p.da, N, H, W, H, W, 3, 1, 1), st);
     LAUNCHED("stem_conv");
-    // norm1 + ReLU: dx (fp32, over the output gradient's NHWC copy, which nothing reads any more)
-    SBnArgs a = bn_args(p, p.xh, nullptr, nullptr, prm->norm1_w, prm->norm1_b, nullptr, p.stats1, true);
+    // norm1 + ReLU: dx (fp32)
+    SBnArgs a = bn_args(p, x, nullptr, nullptr, prm->norm1_w, prm->norm1_b, nullptr, p.stats1, true);
     a.da = p.da; a.gpart = p.gpart;
     launch_bn_bwd_stats(a, st);
     LAUNCHED("bn_bwd_stats");
-    a.dh = p.gf;
+    a.dh = dx;
     if (want_p) { a.dgamma = grads->norm1_w; a.dbeta = grads->norm1_b; }
     launch_bn_bwd_dx(a, st);
     LAUNCHED("bn_bwd_dx");
-    if (d_x) {
-      launch_stem_to_nchw(p.gf, d_x, N, C, HW, st);
-      LAUNCHED("stem_to_nchw");
-    }
   }
   if (want_time) {
     SBnReduceArgs r;
@@ -278,6 +219,77 @@ int node_bnfunc_bwd(const node_bnfunc_shape* shape, const node_bnfunc_params* pr
     r.nchunk = p.nchunk; r.C = C; r.t = t; r.d_t = d_t; r.want_params = want_p ? 1 : 0;
     launch_bn_reduce(r, st);
     LAUNCHED("bn_reduce");
+  }
+  return NODE_OK;
+}
+
+}  // namespace node
+
+using namespace node;
+
+namespace {
+int check_ptr(const void* p, const char* what, bool required) {
+  if (!p) return required ? fail(NODE_ERR_NULL, "%s is NULL", what) : NODE_OK;
+  if (((uintptr_t)p) & 15) return fail(NODE_ERR_ARG, "%s must be 16-byte aligned", what);
+  return NODE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t node_bnfunc_workspace_bytes(const node_bnfunc_shape* shape, int keep_for_backward) {
+  if (check_bn_shape(shape) != NODE_OK) return 0;
+  return make_bn_plan(shape, keep_for_backward != 0, nullptr).bytes;
+}
+
+int node_bnfunc_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* prm, const float* t, const float* x, float* out,
+                    int keep_for_backward, void* ws, size_t ws_bytes, void* stream) {
+  int rc = check_bn_shape(shape);
+  if (rc != NODE_OK) return rc;
+  if ((rc = check_bn_tensors(prm, "params")) != NODE_OK) return rc;
+  if (!t) return fail(NODE_ERR_NULL, "t is NULL (a device scalar)");
+  if (((uintptr_t)t) & 3) return fail(NODE_ERR_ARG, "t must be 4-byte aligned");
+  if ((rc = check_ptr(x, "x", true)) != NODE_OK || (rc = check_ptr(out, "out", true)) != NODE_OK) return rc;
+  if (!ws) return fail(NODE_ERR_NULL, "workspace is NULL");
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+  const BnPlan p = make_bn_plan(shape, keep_for_backward != 0, ws);
+  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "bnfunc workspace too small: %zu < %zu", ws_bytes, p.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  const int N = p.N, C = p.C, HW = p.H * p.W;
+
+  if ((rc = bn_prepare(p, prm, keep_for_backward != 0, st)) != NODE_OK) return rc;
+  launch_stem_from_nchw(x, p.xh, nullptr, 0, N, C, HW, st);
+  LAUNCHED("stem_from_nchw");
+  // (the output gradient's NHWC copy of the backward goes where this forward's NHWC output was: p.gf = p.y)
+  if ((rc = bn_eval_fwd(p, prm, t, p.xh, p.y, 1.0f, st)) != NODE_OK) return rc;
+  launch_stem_to_nchw(p.y, out, N, C, HW, st);
+  return launch_ok("node_bnfunc_fwd");
+}
+
+int node_bnfunc_bwd(const node_bnfunc_shape* shape, const node_bnfunc_params* prm, const float* t, const float* grad_out,
+                    const node_bnfunc_grads* grads, float* d_x, float* d_t, void* ws, size_t ws_bytes, void* stream) {
+  int rc = check_bn_shape(shape);
+  if (rc != NODE_OK) return rc;
+  if ((rc = check_bn_tensors(prm, "params")) != NODE_OK) return rc;
+  if (grads && (rc = check_bn_tensors(grads, "grads")) != NODE_OK) return rc;
+  if (!t) return fail(NODE_ERR_NULL, "t is NULL (a device scalar)");
+  if ((((uintptr_t)t) & 3) || (((uintptr_t)d_t) & 3)) return fail(NODE_ERR_ARG, "t and d_t must be 4-byte aligned");
+  if ((rc = check_ptr(grad_out, "grad_out", true)) != NODE_OK || (rc = check_ptr(d_x, "d_x", false)) != NODE_OK) return rc;
+  if (!ws) return fail(NODE_ERR_NULL, "workspace is NULL");
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+  const BnPlan p = make_bn_plan(shape, true, ws);
+  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "bnfunc workspace too small: %zu < %zu", ws_bytes, p.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  const int N = p.N, C = p.C, HW = p.H * p.W;
+
+  launch_stem_from_nchw(grad_out, p.gf, nullptr, 0, N, C, HW, st);
+  LAUNCHED("stem_from_nchw");
+  // norm1's dx goes over the output gradient's NHWC copy, which nothing reads any more by then
+  if ((rc = bn_eval_bwd(p, prm, t, p.xh, p.gf, 1.0f, grads, p.gf, d_x != nullptr, d_t, st)) != NODE_OK) return rc;
+  if (d_x) {
+    launch_stem_to_nchw(p.gf, d_x, N, C, HW, st);
+    LAUNCHED("stem_to_nchw");
   }
   return NODE_OK;
 }

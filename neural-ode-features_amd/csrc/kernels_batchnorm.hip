@@ -235,8 +235,12 @@ __global__ __launch_bounds__(256) void k_bn_apply(const SBnArgs a) {
       u[k] = (a.relu && y < 0.f) ? 0.f : y;
     }
     const size_t o = (size_t)r * a.C + g.c;
-    if (a.y) store8(a.y + o, u);
     if (a.a3) store_triples(a.a3 + o, a.a_plane, u);
+    if (a.y) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) u[k] *= a.out_scale;
+      store8(a.y + o, u);
+    }
   }
 }
 
@@ -265,7 +269,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_stats(const SBnArgs a) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float xh = bn_xhat(u[k], mu[k], rs[k]);
-      const float d = (a.relu && bn_y(xh, ga[k], be[k]) <= 0.f) ? 0.f : dy[k];
+      const float d = (a.relu && bn_y(xh, ga[k], be[k]) <= 0.f) ? 0.f : a.da_scale * dy[k];
       sA[k] += d;
       sB[k] = __builtin_fmaf(d, xh, sB[k]);
     }
@@ -340,7 +344,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_dx(const SBnArgs a) {
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       const float xh = bn_xhat(u[k], mu[k], rs[k]);
-      const float d = (a.relu && bn_y(xh, ga[k], be[k]) <= 0.f) ? 0.f : dy[k];
+      const float d = (a.relu && bn_y(xh, ga[k], be[k]) <= 0.f) ? 0.f : a.da_scale * dy[k];
       u[k] = rs[k] * ga[k] * __builtin_fmaf(-xh, mB[k], d - mA[k]);     // (explicit: both instances of this kernel round alike)
     }
     const size_t o = (size_t)r * a.C + g.c;
@@ -527,6 +531,43 @@ __global__ __launch_bounds__(256) void k_bn_reduce(const SBnReduceArgs a) {
   }
 }
 
+// ============================================================================
+// the small passes of a solve: <a, b> in two stages (fp64 partials, one order), y += x, a device scalar
+// ============================================================================
+__global__ __launch_bounds__(256) void k_bn_dot(const float* __restrict__ x, const float* __restrict__ y, size_t n4, double* __restrict__ part) {
+  __shared__ double red[256];
+  const int t = threadIdx.x;
+  const size_t stride = (size_t)gridDim.x * 256;
+  double s = 0.0;
+  for (size_t i = (size_t)blockIdx.x * 256 + t; i < n4; i += stride) {
+    const float4 a = reinterpret_cast<const float4*>(x)[i], b = reinterpret_cast<const float4*>(y)[i];
+    s += ((double)a.x * (double)b.x + (double)a.y * (double)b.y) + ((double)a.z * (double)b.z + (double)a.w * (double)b.w);
+  }
+  red[t] = s;
+  __syncthreads();
+  for (int w = 128; w > 0; w >>= 1) {
+    if (t < w) red[t] += red[t + w];
+    __syncthreads();
+  }
+  if (t == 0) part[blockIdx.x] = red[0];
+}
+__global__ __launch_bounds__(64) void k_bn_dot_final(const double* __restrict__ part, int nblk, float* __restrict__ out) {
+  if (threadIdx.x != 0) return;
+  double s = 0.0;
+  for (int i = 0; i < nblk; ++i) s += part[i];
+  *out = (float)s;
+}
+__global__ __launch_bounds__(256) void k_bn_add(float* __restrict__ y, const float* __restrict__ x, size_t n4) {
+  const size_t stride = (size_t)gridDim.x * 256;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    float4 a = reinterpret_cast<float4*>(y)[i];
+    const float4 b = reinterpret_cast<const float4*>(x)[i];
+    a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    reinterpret_cast<float4*>(y)[i] = a;
+  }
+}
+__global__ void k_bn_set_scalar(float* dst, float v) { *dst = v; }
+
 }  // namespace
 
 // ============================================================================
@@ -566,5 +607,18 @@ void launch_bn_reduce(const SBnReduceArgs& a, hipStream_t s) {
   const unsigned grid = (a.want_params ? 2u * ((unsigned)a.C * 9 + (unsigned)(a.C >> 6)) : 0u) + 1u;
   hipLaunchKernelGGL(k_bn_reduce, dim3(grid), dim3(256), 0, s, a);
 }
+static unsigned flat_blocks(size_t n4, unsigned cap) {
+  const size_t b = (n4 + 255) / 256;
+  return b > cap ? cap : b < 1 ? 1u : (unsigned)b;
+}
+void launch_bn_dot(const float* a, const float* b, size_t n, double* part, float* out, hipStream_t s) {
+  const unsigned blocks = flat_blocks(n / 4, BN_DOT_BLOCKS);
+  hipLaunchKernelGGL(k_bn_dot, dim3(blocks), dim3(256), 0, s, a, b, n / 4, part);
+  hipLaunchKernelGGL(k_bn_dot_final, dim3(1), dim3(64), 0, s, part, (int)blocks, out);
+}
+void launch_bn_add(float* y, const float* x, size_t n, hipStream_t s) {
+  hipLaunchKernelGGL(k_bn_add, dim3(flat_blocks(n / 4, 2048)), dim3(256), 0, s, y, x, n / 4);
+}
+void launch_bn_set_scalar(float* dst, float v, hipStream_t s) { hipLaunchKernelGGL(k_bn_set_scalar, dim3(1), dim3(1), 0, s, dst, v); }
 
 }  // namespace node

@@ -396,6 +396,11 @@ def _odeint_impl(func, y0, t, rtol, atol, method, options, adjoint=True, last_on
         # device-resident step controller (generic.py).  Replay lists / dt logs are features of the fused solves.
         if options and any(k in options for k in ('forced_dts', 'forced_dts_bwd', 'record_dt')):
             raise NotImplementedError('replay / dt-log options are not available on the generic solver')
+        # `norm='batch'` dynamics with `ODEfunc.batch_solve` on: the whole solve inside the library (bnsolve.py)
+        from . import bnsolve
+        taken = bnsolve.plan(func, y0, method_id, options, len(times))
+        if taken is not None:
+            return bnsolve.odeint_batch(func, taken, y0, times, rtol, atol, method_id, last_only=last_only)
         from . import generic
         out = generic.odeint_generic(func, y0, times, rtol, atol, method_id, options)
         return out[-1] if last_only else out

@@ -54,9 +54,15 @@ class ODEfunc(nn.Module):
     With `norm='batch'` a call on a HIP fp32 batch of a shape the library takes (bnfunc.plan) is ONE autograd node on the
     package's kernels (bnfunc._BatchOdeFn: forward, and a backward that returns the gradients of t, x and the parameters);
     `ODEfunc.fused_batch = False` switches that off for every instance (A/B measurements, tests).  Every other call runs
-    the module operations below."""
+    the module operations below.
+
+    `batch_solve = True` (off by default; `resnet.build_model` sets it on the `norm='batch'` models it builds) hands a whole
+    `odeint` / `odeint_adjoint` of such a function to the library (bnsolve.py: `node_bnsolve_fwd / node_bnsolve_adjoint`): the
+    state in the BatchNorm kernels' layout from the first stage to the last, the parameters prepared once per solve, no Python
+    between two evaluations.  Without it such solves run the generic solver, which calls this module per evaluation."""
 
     fused_batch = True
+    batch_solve = False
 
     def __init__(self, dim, norm='group'):
         super().__init__()

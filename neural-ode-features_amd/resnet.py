@@ -226,4 +226,11 @@ def build_model(params, in_ch, out):
         return ResNet(in_ch, **common)
     if kind != 'odenet':
         raise ValueError('unknown model %r (resnet or odenet)' % (kind,))
-    return ODENet(in_ch, method=get('method', 'dopri5'), tol=get('tol', 1e-3), adjoint=get('adjoint', False), **common)
+    model = ODENet(in_ch, method=get('method', 'dopri5'), tol=get('tol', 1e-3), adjoint=get('adjoint', False), **common)
+    if common['norm'] == 'batch':
+        # the command lines solve batch-norm dynamics inside the library (bnsolve.py); the class default stays the generic solver
+        from .modules import ODEfunc
+        for m in model.modules():
+            if isinstance(m, ODEfunc):
+                m.batch_solve = True
+    return model
