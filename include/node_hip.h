@@ -593,6 +593,15 @@ int node_bnfunc_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* pa
                     int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
 int node_bnfunc_bwd(const node_bnfunc_shape* shape, const node_bnfunc_params* params, const float* t, const float* grad_out,
                     const node_bnfunc_grads* grads, float* d_x, float* d_t, void* ws, size_t ws_bytes, void* stream);
+/* Diagnostics (tests; ABI 6): the launch plan node_bnfunc_fwd / _bwd and the node_bnsolve_* calls make for a shape, taken from the
+ * plan itself.  Host only, no launch, needs no GPU.  Every BatchNorm pass runs nchunk chunks of chunk_rows rows (the last one
+ * last_chunk_rows) by column_tiles blocks of 64 channels, a thread walking every 32nd row of its chunk; each of the two weight
+ * gradients is split over wgrad_nsplit shares of wgrad_rows_per_split rows, which the backward's reduction launch sums.
+ * Returns what the other calls return for a refused shape, NODE_ERR_NULL for a missing argument. */
+typedef struct node_bnfunc_info {
+  int32_t rows, chunk_rows, nchunk, last_chunk_rows, column_tiles, wgrad_nsplit, wgrad_rows_per_split;
+} node_bnfunc_info;
+int node_bnfunc_describe(const node_bnfunc_shape* shape, node_bnfunc_info* out);
 
 /* A whole SOLVE of these dynamics, forward and continuous adjoint: what the generic solver does around node_bnfunc_fwd / _bwd
  * (stage states, Hairer's initial step, error norms, accept / reject, dense output, FSAL: the node_flat_* kernels), driven from

@@ -51,7 +51,7 @@ EXPORTS = [
     'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd', 'node_convstem_bwd_dx',
     'node_ministem_workspace_bytes', 'node_ministem_fwd', 'node_ministem_bwd',
     'node_pool_fwd', 'node_pool_bwd',
-    'node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd',
+    'node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd', 'node_bnfunc_describe',
     'node_bnsolve_workspace_bytes', 'node_bnsolve_fwd', 'node_bnsolve_adjoint',
 ]
 
@@ -163,6 +163,19 @@ class NodeBnfuncShape(C.Structure):
 
 class NodeBnfuncParams(C.Structure):        # node_bnfunc_params and node_bnfunc_grads share this layout
     _fields_ = [(k, C.c_void_p) for k in BNFUNC_PARAM_FIELDS]
+
+
+class NodeBnfuncInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('rows', 'chunk_rows', 'nchunk', 'last_chunk_rows', 'column_tiles', 'wgrad_nsplit',
+                                         'wgrad_rows_per_split')]
+
+
+def describe_bnfunc(n, c, h, w, eps=1e-5):
+    """The launch plan of the `norm='batch'` node and solves for an [n, c, h, w] state: dict of node_bnfunc_info.  Needs no GPU;
+    raises NodeHipError for a shape the node refuses."""
+    info = NodeBnfuncInfo()
+    check(load().node_bnfunc_describe(C.byref(NodeBnfuncShape(n, c, h, w, eps)), C.byref(info)))
+    return {k: getattr(info, k) for k, _ in info._fields_}
 
 
 class NodeBnsolveOpts(C.Structure):
@@ -429,6 +442,8 @@ def load():
     lib.node_bnfunc_fwd.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, vp, i32, vp, sz, vp]
     lib.node_bnfunc_bwd.restype = i32
     lib.node_bnfunc_bwd.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, P(NodeBnfuncParams), vp, vp, vp, sz, vp]
+    lib.node_bnfunc_describe.restype = i32
+    lib.node_bnfunc_describe.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncInfo)]
     lib.node_bnsolve_workspace_bytes.restype = sz
     lib.node_bnsolve_workspace_bytes.argtypes = [P(NodeBnfuncShape), i32, i32, i32]
     lib.node_bnsolve_fwd.restype = i32

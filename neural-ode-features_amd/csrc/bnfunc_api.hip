@@ -243,6 +243,19 @@ size_t node_bnfunc_workspace_bytes(const node_bnfunc_shape* shape, int keep_for_
   return make_bn_plan(shape, keep_for_backward != 0, nullptr).bytes;
 }
 
+int node_bnfunc_describe(const node_bnfunc_shape* shape, node_bnfunc_info* out) {
+  if (!out) return fail(NODE_ERR_NULL, "out is NULL");
+  memset(out, 0, sizeof(*out));
+  const int rc = check_bn_shape(shape);
+  if (rc != NODE_OK) return rc;
+  const BnPlan p = make_bn_plan(shape, true, nullptr);      // the backward's plan: the same chunks as the forward's, plus the two weight gradients
+  out->rows = p.R; out->chunk_rows = p.cr; out->nchunk = p.nchunk;
+  out->last_chunk_rows = p.R - (p.nchunk - 1) * p.cr;
+  out->column_tiles = p.C >> 6;
+  out->wgrad_nsplit = p.w1.nsplit; out->wgrad_rows_per_split = p.w1.rps;      // (w2 is taken with the same arguments)
+  return NODE_OK;
+}
+
 int node_bnfunc_fwd(const node_bnfunc_shape* shape, const node_bnfunc_params* prm, const float* t, const float* x, float* out,
                     int keep_for_backward, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_bn_shape(shape);

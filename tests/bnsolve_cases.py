@@ -22,7 +22,10 @@ SHAPES = [(4, 64, 6, 6),     # 144 rows: five statistic chunks, the last one par
           (2, 64, 6, 5),     # non-square
           (1, 64, 3, 3),     # one sample, the smallest image, one chunk
           (2, 192, 7, 7)]    # three column tiles, not a power of two
-SPLITK_SHAPE = (64, 64, 8, 8)      # 4096 rows: the split-K weight gradient
+SPLITK_SHAPE = (64, 64, 8, 8)      # 4096 rows in 128 statistic chunks of 32 rows (one trip of the passes' row loops, like every shape above); a
+#                                    weight gradient split 64 ways
+MULTIROW_SHAPE = (84, 64, 7, 7)    # 4116 rows in chunks of 64, the last one of 20: second trips of the row loops, where out_scale, da_scale and
+#                                    the stage-slot writes of a solve had never run (tests/test_bnsolve_host.py asserts the regime)
 GRIDS = [(0.0, 1.0), (0.0, 0.3, 0.55, 1.0), (1.0, 0.4, 0.0)]
 E_FLOOR = {'out': 2e-6, 'gy': 2e-6, 'gp': 1.5e-3}
 

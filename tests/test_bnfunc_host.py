@@ -1,6 +1,7 @@
 """Host side (no GPU) of the `norm='batch'` dynamics node (bnfunc.py, csrc/bnfunc_api.hip): the command line, the argument
-checks of node_bnfunc_*, the ctypes layouts, the CPU path of `ODEfunc(C, norm='batch')`, and the seeds of
-tests/test_gpu_bnfunc.py."""
+checks of node_bnfunc_*, the ctypes layouts, the CPU path of `ODEfunc(C, norm='batch')`, the seeds of
+tests/test_gpu_bnfunc.py, and the conditions of its multi-row cases: their launch regimes through node_bnfunc_describe, the
+signs of their special parameter sets, the margins of their ordinary seeds."""
 import ctypes as C
 import os
 import subprocess
@@ -101,6 +102,8 @@ def test_ctypes_layouts_match_the_header(tmp_path):
         'node_bnfunc_shape': (_lib.NodeBnfuncShape, ['n', 'channels', 'h', 'w', 'eps']),
         'node_bnfunc_params': (_lib.NodeBnfuncParams, list(_lib.BNFUNC_PARAM_FIELDS)),
         'node_bnfunc_grads': (_lib.NodeBnfuncParams, list(_lib.BNFUNC_PARAM_FIELDS)),
+        'node_bnfunc_info': (_lib.NodeBnfuncInfo, ['rows', 'chunk_rows', 'nchunk', 'last_chunk_rows', 'column_tiles', 'wgrad_nsplit',
+                                                   'wgrad_rows_per_split']),
     }
     lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "node_hip.h"', 'int main(void) {']
     for name, (_, fields) in structs.items():
@@ -117,7 +120,9 @@ def test_ctypes_layouts_match_the_header(tmp_path):
         assert int(got[name]) == C.sizeof(ct), name
         for f in fields:
             assert int(got['%s.%s' % (name, f)]) == getattr(ct, f).offset, (name, f)
-    for name in ('node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd'):
+    assert [k for k, _ in _lib.NodeBnfuncInfo._fields_] == structs['node_bnfunc_info'][1]
+    assert all(ct is C.c_int32 for _, ct in _lib.NodeBnfuncInfo._fields_)
+    for name in ('node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd', 'node_bnfunc_describe'):
         assert name in _lib.EXPORTS and hasattr(_lib.load(), name)
     assert _lib.load().node_abi_version() == 6 == _lib.NODE_ABI_VERSION
     # the ten tensors are ODEfunc's own, in named_parameters() order
@@ -156,3 +161,76 @@ def test_seeds_of_the_gpu_cases_keep_every_relu_mask(case):
     fp64 run's (bnfunc_cases.py has the recipe)."""
     agree, margin = B.masks_agree(case, B.SEEDS[case])
     assert agree and margin > 0
+
+
+def _id(c):
+    return 'n%d_c%d_%dx%d' % c
+
+
+def test_plan_query_is_consistent_and_refuses_what_the_node_refuses():
+    from neural_ode_features_amd import _lib
+    lib = _lib.load()
+    info = _lib.NodeBnfuncInfo()
+    assert lib.node_bnfunc_describe(None, C.byref(info)) == NODE_ERR_NULL
+    assert lib.node_bnfunc_describe(C.byref(_lib.NodeBnfuncShape(2, 64, 8, 8, 1e-5)), None) == NODE_ERR_NULL
+    assert lib.node_bnfunc_describe(C.byref(_lib.NodeBnfuncShape(2, 96, 8, 8, 1e-5)), C.byref(info)) == _lib.NODE_ERR_UNSUPPORTED
+    assert info.rows == 0 and 'multiple of 64' in lib.node_last_error().decode()
+    with pytest.raises(_lib.NodeHipError):
+        _lib.describe_bnfunc(2, 64, 2, 8)
+    for case in list(B.CASES) + list(B.MULTI_CASES) + [(128, 256, 8, 8)]:
+        d = _lib.describe_bnfunc(*case)
+        assert d['rows'] == case[0] * case[2] * case[3] and d['column_tiles'] * 64 == case[1]
+        assert d['chunk_rows'] % 32 == 0 and (d['nchunk'] - 1) * d['chunk_rows'] + d['last_chunk_rows'] == d['rows']
+        assert 0 < d['last_chunk_rows'] <= d['chunk_rows']
+        assert (d['wgrad_nsplit'] - 1) * d['wgrad_rows_per_split'] < d['rows'] <= d['wgrad_nsplit'] * d['wgrad_rows_per_split']
+    assert _lib.describe_bnfunc(128, 256, 8, 8)['chunk_rows'] > 64         # the CIFAR training step: four trips of the row loops
+
+
+@pytest.mark.parametrize('case', B.CASES, ids=_id)
+def test_the_first_cases_all_run_one_trip_of_the_row_loops(case):
+    """Why B.MULTI_CASES exists: every case of B.CASES has chunks of 32 rows, so no thread of a BatchNorm pass takes a second
+    trip round `for (r = r0 + rr; r < r1; r += 32)`."""
+    from neural_ode_features_amd import _lib
+    assert _lib.describe_bnfunc(*case)['chunk_rows'] == 32
+
+
+@pytest.mark.parametrize('case', B.MULTI_CASES, ids=_id)
+def test_new_cases_are_in_the_regimes_they_are_there_for(case):
+    from neural_ode_features_amd import _lib
+    d = _lib.describe_bnfunc(*case)
+    assert B.MULTI_CASES[case], case
+    for regime in B.MULTI_CASES[case]:
+        assert B.REGIMES[regime](d), (case, regime, d)
+
+
+def test_new_cases_cover_every_regime_between_them():
+    named = {r for regimes in B.MULTI_CASES.values() for r in regimes}
+    assert named == set(B.REGIMES), named ^ set(B.REGIMES)
+    # what the lane model says of the split counts the suite runs: 1, 2, 4 remainder only; 8, 64 loop only
+    for ns in (1, 2, 4):
+        assert B.reduce_lanes(ns)[0] == set()
+    for ns in (8, 64):
+        assert B.reduce_lanes(ns) == ({0, 1, 2, 3}, set())
+    assert B.reduce_lanes(5) == ({0}, {1, 2, 3}) and B.reduce_lanes(52) == ({0, 1, 2, 3}, {0, 1, 2, 3})
+
+
+@pytest.mark.parametrize('mode', ['kinkfree', 'split'])
+@pytest.mark.parametrize('case', B.MULTI_CASES, ids=_id)
+def test_special_parameter_sets_keep_every_preactivation_clear_of_zero(case, mode):
+    """A condition of the GPU tests, not a measurement: in fp64 every channel of norm1's and norm2's output has one sign over all rows
+    and no |pre-activation| is under 0.1; 'split' masks exactly half the channels, 'kinkfree' none."""
+    constant, on, margin = B.sign_condition(case, B.KINK_FREE_SEED, mode)
+    assert constant and margin >= 0.1, (constant, margin)
+    assert on == ([0.5, 0.5] if mode == 'split' else [1.0, 1.0]), on
+
+
+@pytest.mark.parametrize('case', B.MULTI_CASES, ids=_id)
+def test_ordinary_seeds_of_the_new_cases_are_admissible(case):
+    """The kept seed alone is re-checked (bnfunc_cases.py has the recipe and the search): every ReLU mask of the fp32 CPU run agrees
+    with the fp64 run's, and margin / error is at least that of the closest case the suite ran before, computed here."""
+    if case not in B.MULTI_SEEDS:
+        return                   # no admissible seed in 0..199: the case runs kink-free and split only
+    need = B.margin_ratio(*B.RATIO_YARDSTICK)[2]
+    agree, margin, ratio = B.margin_ratio(case, B.MULTI_SEEDS[case])
+    print('%s seed %d: margin %.2e, margin / error %.2f (needed %.2f)' % (case, B.MULTI_SEEDS[case], margin, ratio, need))
+    assert agree and margin > 0 and ratio >= need, (agree, margin, ratio, need)

@@ -33,6 +33,19 @@ def test_ctypes_layout_of_the_options_matches_the_header(tmp_path):
     assert _lib.load().node_abi_version() == 6 == _lib.NODE_ABI_VERSION          # additive
 
 
+def test_launch_regimes_of_the_solve_shapes():
+    """A solve runs the plan node_bnfunc_describe reports (bnsolve_api.hip takes make_bn_plan's): every shape of SHAPES and
+    SPLITK_SHAPE has chunks of 32 rows -- one trip of the BatchNorm passes' row loops -- and MULTIROW_SHAPE is there for the second
+    trip and a last chunk shorter than the 32 row slots."""
+    from neural_ode_features_amd import _lib
+    from tests import bnsolve_cases as S
+    for shape in S.SHAPES + [S.SPLITK_SHAPE]:
+        assert _lib.describe_bnfunc(*shape)['chunk_rows'] == 32, shape
+    assert _lib.describe_bnfunc(*S.SPLITK_SHAPE)['wgrad_nsplit'] > 8
+    d = _lib.describe_bnfunc(*S.MULTIROW_SHAPE)
+    assert d['chunk_rows'] > 32 and 0 < d['last_chunk_rows'] < 32 and d['wgrad_nsplit'] > 8, d
+
+
 def test_workspace_query_sizes_and_refusals():
     from neural_ode_features_amd import _lib
     lib = _lib.load()
