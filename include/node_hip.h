@@ -603,6 +603,44 @@ typedef struct node_bnfunc_info {
 } node_bnfunc_info;
 int node_bnfunc_describe(const node_bnfunc_shape* shape, node_bnfunc_info* out);
 
+/* The residual trunk of the ResNet baseline with norm = 'batch' -- model.py:79 with model.py:274: `blocks` x
+ * ResBlock(channels, channels, norm='batch'), stride 1, identity shortcut.  Per block
+ *     a = relu(norm1(x));  h = conv1(a);  y = conv2(relu(norm2(h))) + x
+ * with norm = nn.BatchNorm2d(channels, track_running_stats=False) (statistics of the batch in training and evaluation alike)
+ * and both convolutions 3x3 / stride 1 / padding 1 without bias.  The residual trunk above in every respect but the norm:
+ * the same shape and block structures (parameter order n1_w, n1_b, c1_w, n2_w, n2_b, c2_w), NCHW at the boundary, optional
+ * taps, keep_for_backward, one workspace per forward in flight; the BatchNorm passes are those of the batch-norm dynamics
+ * (two-stage statistics combined by Chan's formula, fp64 backward partials), and the gradient of a block's input leaves its
+ * norm1 backward pass with the shortcut's gradient already added.
+ *   channels: a multiple of 64 in [64, 4096] (192 is fine); blocks >= 1; any n, h, w >= 1; tensors under 2^31 elements.
+ *   Anything else: NODE_ERR_UNSUPPORTED with a message, and the workspace-size call returns 0.  Every tensor 16-byte aligned
+ *   (NODE_ERR_ARG), the workspace 256-byte aligned.
+ * The backward writes (does not accumulate) every parameter gradient and d_x (required).  No floating-point atomics: every
+ * sum runs in a fixed order, so results are bit-reproducible run to run.  The calls never synchronise, allocate device memory
+ * or read back.  The describe call is the one of the batch-norm dynamics for this plan (host only, needs no GPU). */
+size_t node_bntrunk_workspace_bytes(const node_trunk_shape* shape, int keep_for_backward);
+int node_bntrunk_fwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* x, float* out, float* taps,
+                     int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_bntrunk_bwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* grad_out,
+                     const node_trunk_block_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+int node_bntrunk_describe(const node_trunk_shape* shape, node_bnfunc_info* out);
+
+/* Classifier head of a norm = 'batch' net, up to (not including) the Linear layer -- model.py:231-250 with model.py:274:
+ * BatchNorm2d(channels, track_running_stats=False) -> ReLU -> AdaptiveAvgPool2d((1,1)) -> [Dropout] -> Flatten:
+ *     pooled[n, c] = scale[n, c] * mean over pixels of relu(gamma[c] * xhat + beta[c])
+ * with xhat normalised by the mean and biased variance of channel c over all n h w values.  z, dz: [n, channels, h, w] NCHW;
+ * gamma, beta, dgamma, dbeta: [channels]; scale: [n, channels] dropout mask / (1 - p) as the caller's RNG produced it, or NULL;
+ * pooled, g_pooled: [n, channels]; stats: [2, channels] (mean, 1 / sqrt(var + eps)), kept by the caller for the backward;
+ * scratch: node_bnhead_scratch_bytes bytes, 8-byte aligned, the statistics' partials of the call in flight (each call may be
+ * given another).  Two launches each on `stream`.  Shapes: channels as above, tensors under 2^31 elements; NODE_ERR_UNSUPPORTED
+ * otherwise (the scratch-size call returns 0).  Two-stage statistics with centred second moments, fp64 partials in the
+ * backward, no atomics: the same bits on every run. */
+size_t node_bnhead_scratch_bytes(const node_bnfunc_shape* shape);
+int node_bnhead_fwd(const node_bnfunc_shape* shape, const float* z, const float* gamma, const float* beta, const float* scale,
+                    float* pooled, float* stats, void* scratch, void* stream);
+int node_bnhead_bwd(const node_bnfunc_shape* shape, const float* z, const float* gamma, const float* beta, const float* scale,
+                    const float* stats, const float* g_pooled, float* dz, float* dgamma, float* dbeta, void* scratch, void* stream);
+
 /* A whole SOLVE of these dynamics, forward and continuous adjoint: what the generic solver does around node_bnfunc_fwd / _bwd
  * (stage states, Hairer's initial step, error norms, accept / reject, dense output, FSAL: the node_flat_* kernels), driven from
  * inside the library.  The state stays in the BatchNorm kernels' NHWC layout from the first stage to the last (NCHW at the

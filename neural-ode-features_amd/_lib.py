@@ -53,6 +53,8 @@ EXPORTS = [
     'node_pool_fwd', 'node_pool_bwd',
     'node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd', 'node_bnfunc_describe',
     'node_bnsolve_workspace_bytes', 'node_bnsolve_fwd', 'node_bnsolve_adjoint',
+    'node_bntrunk_workspace_bytes', 'node_bntrunk_fwd', 'node_bntrunk_bwd', 'node_bntrunk_describe',
+    'node_bnhead_scratch_bytes', 'node_bnhead_fwd', 'node_bnhead_bwd',
 ]
 
 
@@ -175,6 +177,14 @@ def describe_bnfunc(n, c, h, w, eps=1e-5):
     raises NodeHipError for a shape the node refuses."""
     info = NodeBnfuncInfo()
     check(load().node_bnfunc_describe(C.byref(NodeBnfuncShape(n, c, h, w, eps)), C.byref(info)))
+    return {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def describe_bntrunk(n, c, h, w, blocks=6, eps=1e-5):
+    """The launch plan of the `norm='batch'` residual trunk for an [n, c, h, w] state: dict of node_bnfunc_info.  Needs no GPU;
+    raises NodeHipError for a shape the node refuses."""
+    info = NodeBnfuncInfo()
+    check(load().node_bntrunk_describe(C.byref(NodeTrunkShape(n, c, h, w, blocks, eps)), C.byref(info)))
     return {k: getattr(info, k) for k, _ in info._fields_}
 
 
@@ -454,6 +464,20 @@ def load():
                                          P(NodeBnsolveOpts), vp, P(NodeBnfuncParams), P(NodeStats), vp, sz, vp]
     lib.node_trunk_bwd.restype = i32
     lib.node_trunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
+    lib.node_bntrunk_workspace_bytes.restype = sz
+    lib.node_bntrunk_workspace_bytes.argtypes = [P(NodeTrunkShape), i32]
+    lib.node_bntrunk_fwd.restype = i32
+    lib.node_bntrunk_fwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, vp, vp, i32, vp, sz, vp]
+    lib.node_bntrunk_bwd.restype = i32
+    lib.node_bntrunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
+    lib.node_bntrunk_describe.restype = i32
+    lib.node_bntrunk_describe.argtypes = [P(NodeTrunkShape), P(NodeBnfuncInfo)]
+    lib.node_bnhead_scratch_bytes.restype = sz
+    lib.node_bnhead_scratch_bytes.argtypes = [P(NodeBnfuncShape)]
+    lib.node_bnhead_fwd.restype = i32
+    lib.node_bnhead_fwd.argtypes = [P(NodeBnfuncShape), vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.node_bnhead_bwd.restype = i32
+    lib.node_bnhead_bwd.argtypes = [P(NodeBnfuncShape), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.node_downconv_workspace_bytes.restype = sz
     lib.node_downconv_workspace_bytes.argtypes = [P(NodeDownConvShape), i32]
     lib.node_downconv_fwd.restype = i32

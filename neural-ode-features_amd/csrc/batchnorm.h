@@ -44,6 +44,8 @@ struct SBnArgs {
   // sign on `da` of the FIRST backward pass of an evaluation reaches every gradient it returns.
   float out_scale = 1.0f;  // on the fp32 output `y` of the apply pass (the triples are not scaled)
   float da_scale = 1.0f;   // on every read of `da` in the two backward passes
+  // the residual trunk (bntrunk_api.hip): h also is the block's shortcut, so its gradient is du + skip.  Not with clsp.
+  const float* skip = nullptr;   // nullable fp32 NHWC, added to du before the fp32 store and the triple split (dx pass only)
 };
 // rows per chunk for a tensor of `rows` x C: <= 128 chunks, enough (chunk, channel block) pairs to cover the device
 int bn_chunk_rows(int rows, int C);
@@ -79,6 +81,33 @@ struct SBnReduceArgs {
   int want_params;
 };
 void launch_bn_reduce(const SBnReduceArgs& a, hipStream_t s);
+
+// The classifier head of a `norm='batch'` net (kernels_bnhead.hip): pooled[n][c] = scale[n][c] * mean_px relu(BatchNorm(z)) on the
+// NCHW tensor z [N][C][HW] as the net's body leaves it.  A workgroup = (channel, chunk of S samples), a wave = one (n, c) plane
+// at a time (HW contiguous floats: whole cache lines).  Two launches each way, statistics in the two stages of the passes above.
+constexpr int BNHEAD_MAX_CHUNKS = 32;
+struct SBnHeadArgs {
+  const float* z;          // fp32 NCHW [N][C][HW]
+  const float* gamma;
+  const float* beta;
+  const float* scale;      // nullable [N][C]: the dropout mask / (1 - p)
+  float* pooled;           // [N][C]
+  float* stats;            // [2][C]: batch mean, 1 / sqrt(biased variance + eps): written by the apply pass, read by the backward
+  float* part;             // forward [nchunk][2][C]: (chunk mean, centred second moment)
+  const float* g_pooled;   // backward [N][C]
+  float* dz;               // backward [N][C][HW]
+  double* gpart;           // backward [nchunk][2][C]: (sum dy, sum dy xhat) of the chunk, fp64
+  float* dgamma;           // [C] (written by the chunk-0 workgroups of the dx pass)
+  float* dbeta;
+  int N, C, HW;
+  int chunk_samples, nchunk;   // nchunk <= BNHEAD_MAX_CHUNKS
+  float eps;
+};
+int bnhead_chunk_samples(int N, int C);      // samples per chunk: <= BNHEAD_MAX_CHUNKS chunks, about 2048 workgroups at most
+void launch_bnhead_stats(const SBnHeadArgs& a, hipStream_t s);
+void launch_bnhead_apply(const SBnHeadArgs& a, hipStream_t s);
+void launch_bnhead_bwd_stats(const SBnHeadArgs& a, hipStream_t s);
+void launch_bnhead_bwd_dx(const SBnHeadArgs& a, hipStream_t s);
 
 // The small passes of a whole solve around these dynamics (bnsolve_api.hip); n % 4 == 0, 16-byte aligned tensors.
 // *out = sum a[i] * b[i]: two launches, fp64 partials [BN_DOT_BLOCKS] in a fixed order

@@ -286,8 +286,10 @@ __global__ __launch_bounds__(256) void k_bn_bwd_stats(const SBnArgs a) {
 // backward, stage 2: du = rstd gamma (dy - mean(dy) - xhat mean(dy xhat)); dgamma = sum dy xhat, dbeta = sum dy (chunk 0 writes them)
 // TIME: also the per-class sums of du and the workgroup's share of sum du * T.  Every thread owns 9 x 8 accumulators in LDS
 // (a row's class is one index into them: registers would need a dynamic index).
+// SKIP (only without TIME: the residual trunk's norm1, whose input also is the block's shortcut): the gradient written is du + skip.
+// A variant at compile time, so the two instances the dynamics launch keep their instruction streams.
 // ============================================================================
-template <bool TIME>
+template <bool TIME, bool SKIP = false>
 __global__ __launch_bounds__(256) void k_bn_bwd_dx(const SBnArgs a) {
   extern __shared__ __align__(16) unsigned char dyn[];      // (no static __shared__ next to a dynamic region above 64 KB: the attribute call refuses their sum)
   float* sm = reinterpret_cast<float*>(dyn);                // [4][2][64] doubles
@@ -348,6 +350,12 @@ __global__ __launch_bounds__(256) void k_bn_bwd_dx(const SBnArgs a) {
       u[k] = rs[k] * ga[k] * __builtin_fmaf(-xh, mB[k], d - mA[k]);     // (explicit: both instances of this kernel round alike)
     }
     const size_t o = (size_t)r * a.C + g.c;
+    if constexpr (SKIP) {
+      float sk[8];
+      load8(a.skip + o, sk);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) u[k] += sk[k];
+    }
     if (a.dh) store8(a.dh + o, u);
     if (a.dh3) store_triples(a.dh3 + o, a.dh_plane, u);
     if constexpr (TIME) {
@@ -592,6 +600,8 @@ void launch_bn_bwd_dx(const SBnArgs& a, hipStream_t s) {
     allow_full_lds(reinterpret_cast<const void*>(k_bn_bwd_dx<true>), attr);
     const size_t lds = ((size_t)1152 + 9 * 256 * 8) * sizeof(float) + 9 * 64 * sizeof(double);
     hipLaunchKernelGGL(k_bn_bwd_dx<true>, bn_grid(a), dim3(256), lds, s, a);
+  } else if (a.skip != nullptr) {
+    hipLaunchKernelGGL((k_bn_bwd_dx<false, true>), bn_grid(a), dim3(256), 1152 * sizeof(float), s, a);
   } else {
     hipLaunchKernelGGL(k_bn_bwd_dx<false>, bn_grid(a), dim3(256), 1152 * sizeof(float), s, a);
   }

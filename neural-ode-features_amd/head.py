@@ -4,7 +4,9 @@ and one backward (`node_head_fwd / node_head_bwd`, csrc/kernels_head.hip) instea
 PyTorch kernels.  The dropout mask is drawn by PyTorch's own generator (so seeds reproduce what
 `nn.Dropout` would have drawn on the pooled `[N, C, 1, 1]` tensor) and handed to the kernel as a
 per-(sample, channel) scale.  No CPU or PyTorch fallback inside: callers route non-CUDA / non-fp32
-inputs to the plain module sequence themselves (`FCClassifier.forward`)."""
+inputs to the plain module sequence themselves (`FCClassifier.forward`).  The head of a `norm='batch'`
+net (BatchNorm2d without running statistics in place of the GroupNorm) has kernels of its own, two
+launches each way: `bn_head_pool` (`node_bnhead_fwd / node_bnhead_bwd`, csrc/kernels_bnhead.hip)."""
 from __future__ import annotations
 
 import torch
@@ -60,6 +62,75 @@ def head_pool(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, groups: 
         scale = F.dropout(torch.ones(z.shape[0], z.shape[1], 1, 1, device=z.device, dtype=torch.float32), p, True)
         scale = scale.reshape(z.shape[0], z.shape[1]).contiguous()
     return _HeadPool.apply(z, gamma, beta, scale, groups, eps)
+
+
+class _BnHeadPool(torch.autograd.Function):
+    """The same head behind `nn.BatchNorm2d(C, track_running_stats=False)` (model.py:274): statistics across the batch, so a kernel
+    family of its own (`node_bnhead_fwd / node_bnhead_bwd`, csrc/kernels_bnhead.hip), two launches each way."""
+
+    @staticmethod
+    def forward(ctx, z, gamma, beta, scale, eps):
+        lib = _lib.load()
+        z = z.contiguous()
+        n, c, h, w = z.shape
+        shape = _lib.NodeBnfuncShape(n, c, h, w, eps)
+        g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+        stream = torch.cuda.current_stream(z.device).cuda_stream
+        with torch.cuda.device(z.device):
+            nbytes = lib.node_bnhead_scratch_bytes(shape)
+            if nbytes == 0:
+                _lib.unsupported()
+            pooled = torch.empty(n, c, device=z.device, dtype=torch.float32)
+            stats = torch.empty(2, c, device=z.device, dtype=torch.float32)
+            scratch = torch.empty(nbytes // 8, device=z.device, dtype=torch.float64)
+            _lib.check(lib.node_bnhead_fwd(shape, _ptr(z), _ptr(g), _ptr(b), _ptr(scale), _ptr(pooled), _ptr(stats), _ptr(scratch), stream))
+        ctx.save_for_backward(z, g, b, scale, stats)
+        ctx.shape = (n, c, h, w, eps)
+        return pooled
+
+    @staticmethod
+    def backward(ctx, g_pooled):
+        lib = _lib.load()
+        z, g, b, scale, stats = ctx.saved_tensors
+        n, c, h, w, eps = ctx.shape
+        shape = _lib.NodeBnfuncShape(n, c, h, w, eps)
+        g_pooled = g_pooled.contiguous()
+        if g_pooled.dtype != torch.float32:
+            g_pooled = g_pooled.float()
+        stream = torch.cuda.current_stream(z.device).cuda_stream
+        with torch.cuda.device(z.device):
+            dz = torch.empty_like(z)
+            dgb = torch.empty(2, c, device=z.device, dtype=torch.float32)
+            dgamma, dbeta = dgb.unbind(0)
+            scratch = torch.empty(lib.node_bnhead_scratch_bytes(shape) // 8, device=z.device, dtype=torch.float64)
+            _lib.check(lib.node_bnhead_bwd(shape, _ptr(z), _ptr(g), _ptr(b), _ptr(scale), _ptr(stats), _ptr(g_pooled), _ptr(dz),
+                                           _ptr(dgamma), _ptr(dbeta), _ptr(scratch), stream))
+        return dz, dgamma, dbeta, None, None
+
+
+def bn_head_fusable(z: torch.Tensor, norm) -> bool:
+    """What `bn_head_pool` takes: an fp32 NCHW batch on a HIP device in front of an affine `nn.BatchNorm2d` without running
+    statistics, C a multiple of 64 in [64, 4096], more than one value per channel (N H W = 1 is what nn.BatchNorm2d itself refuses:
+    the module raises it), tensors under 2^31 elements."""
+    if not (isinstance(norm, torch.nn.BatchNorm2d) and norm.affine and not norm.track_running_stats and norm.running_mean is None
+            and not norm._forward_hooks and not norm._forward_pre_hooks):
+        return False
+    if not (torch.is_tensor(z) and z.is_cuda and z.dtype == torch.float32 and z.dim() == 4 and z.shape[0] >= 1):
+        return False
+    n, c, h, w = z.shape
+    return (c == norm.num_features and c % 64 == 0 and 64 <= c <= 4096 and n * h * w > 1 and z.numel() < 2 ** 31
+            and all(p.is_cuda and p.dtype == torch.float32 and p.device == z.device for p in (norm.weight, norm.bias)))
+
+
+def bn_head_pool(z: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float, p: float = 0.0,
+                 training: bool = False) -> torch.Tensor:
+    """pooled[n, c] = dropout(mean_px relu(BatchNorm(z))), batch statistics   -- model.py:239-247 with model.py:274."""
+    scale = None
+    if training and p > 0.0:
+        # exactly the numbers nn.Dropout would multiply the pooled [N, C, 1, 1] tensor by (as head_pool draws them)
+        scale = F.dropout(torch.ones(z.shape[0], z.shape[1], 1, 1, device=z.device, dtype=torch.float32), p, True)
+        scale = scale.reshape(z.shape[0], z.shape[1]).contiguous()
+    return _BnHeadPool.apply(z, gamma, beta, scale, eps)
 
 
 class _GnRelu(torch.autograd.Function):

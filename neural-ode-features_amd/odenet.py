@@ -184,14 +184,16 @@ class FCClassifier(_Wrapped):
         super().__init__(nn.Sequential(*layers))
 
     def forward(self, x):
-        """CUDA fp32 inputs take the fused HIP head (head.py: one launch forward, one backward) for everything
-        in front of the last layer; anything else -- CPU tensors, a body someone has edited beyond what
+        """CUDA fp32 inputs take the fused HIP head (head.py: one launch forward, one backward; two each behind a
+        `norm='batch'` BatchNorm2d that `head.bn_head_fusable` accepts) for everything in front of the last
+        layer; anything else -- CPU tensors, a body someone has edited beyond what
         `ODENet.to_features_extractor` does -- runs the plain module sequence."""
         body = list(self.module.children())
         fusable = (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and len(body) in (5, 6)
-                   and isinstance(body[0], nn.GroupNorm) and body[0].affine and isinstance(body[1], nn.ReLU)
+                   and isinstance(body[1], nn.ReLU)
                    and isinstance(body[2], nn.AdaptiveAvgPool2d) and isinstance(body[-2], Flatten)
-                   and (len(body) == 5 or isinstance(body[3], nn.Dropout)))
+                   and (len(body) == 5 or isinstance(body[3], nn.Dropout))
+                   and ((isinstance(body[0], nn.GroupNorm) and body[0].affine) or self._batch_head(x, body[0])))
         if not fusable:
             return self.module(x)
         pooled = self.pooled(x)
@@ -201,14 +203,25 @@ class FCClassifier(_Wrapped):
             return linear(pooled, last.weight, last.bias)
         return last(pooled)                  # (feature extraction: the classification layer was replaced, model.py:53)
 
+    # a `norm='batch'` head as two launches of the HIP library each way (head.bn_head_pool); False: the module sequence, as before
+    # those kernels existed (A/B runs, tests).  GroupNorm heads do not read it.
+    fused_batch = True
+
+    def _batch_head(self, x, norm):
+        from .head import bn_head_fusable
+        return self.fused_batch and bn_head_fusable(x, norm)
+
     def pooled(self, x):
-        """dropout(mean_px relu(GroupNorm(x))): everything in front of the Linear layer, one launch each way."""
-        from .head import head_pool
+        """dropout(mean_px relu(norm(x))): everything in front of the Linear layer, one launch each way (GroupNorm) or two
+        (BatchNorm: statistics across the batch)."""
+        from .head import bn_head_pool, head_pool
         body = list(self.module.children())
         gn = body[0]
         drop = body[3] if len(body) == 6 else None
-        return head_pool(x, gn.weight, gn.bias, gn.num_groups, gn.eps,
-                         p=drop.p if drop is not None else 0.0, training=self.training and drop is not None)
+        p, training = drop.p if drop is not None else 0.0, self.training and drop is not None
+        if isinstance(gn, nn.BatchNorm2d):
+            return bn_head_pool(x, gn.weight, gn.bias, gn.eps, p=p, training=training)
+        return head_pool(x, gn.weight, gn.bias, gn.num_groups, gn.eps, p=p, training=training)
 
 
 class ODENet(nn.Module):

@@ -6,7 +6,9 @@ outputs of its six blocks).
 `ResidualTrunk` is the `features` member: an `nn.Sequential` of the package's `ResBlock`s (the reference's state_dict
 keys, `features.<i>.norm1.weight`, ...) whose forward and backward on a HIP device are ONE autograd node through the
 library (`node_trunk_fwd / node_trunk_bwd`, csrc/trunk_api.hip): the stem's gather-GEMM convolutions on bf16 triples,
-the residual added in the second convolution's epilogue, NHWC inside, no MIOpen call, no layout transposes.
+the residual added in the second convolution's epilogue, NHWC inside, no MIOpen call, no layout transposes.  A `norm='batch'`
+trunk (`train --model resnet --norm batch`, the net every ODE-Net comparison of the reference is made against) is the same plan
+around the BatchNorm passes of the batch-norm dynamics (`node_bntrunk_fwd / node_bntrunk_bwd`, csrc/bntrunk_api.hip).
 """
 from __future__ import annotations
 
@@ -19,39 +21,57 @@ from torch.autograd.function import once_differentiable
 from . import _lib, workspace
 from .odenet import FCClassifier, ResBlock, _Wrapped, _stem
 
-_FREE = workspace.Carried()       # (device, shape) -> workspaces whose backward has run: free for the next forward of that shape
-_SCRATCH = workspace.Scratch()    # (device, stream, shape) -> the workspace of forwards that keep nothing
-
-
 def _block_params(blk):
     return [blk.norm1.weight, blk.norm1.bias, blk.conv1.weight, blk.norm2.weight, blk.norm2.bias, blk.conv2.weight]
 
 
-def _params_of(seq):
-    """The trunk's tensors, six per block in node_trunk_block order, or None if `seq` is not `blocks` x the reference's
-    ResBlock(C, C) (stride 1, no downsample, GroupNorm(min(32, C), C), 3x3 / 1 / 1 convolutions without bias)."""
+def _norm_form(norm):
+    """'group' / 'batch' for the two norms the library's trunks take, None for anything else: the reference's
+    GroupNorm(min(32, C), C), or its BatchNorm2d(C, track_running_stats=False) (model.py:268-281), affine."""
+    if isinstance(norm, nn.GroupNorm):
+        return 'group' if norm.affine and norm.num_groups == min(32, norm.num_channels) else None
+    if isinstance(norm, nn.BatchNorm2d):
+        # running statistics would have to be updated in training and USED in evaluation: the node does neither
+        return 'batch' if norm.affine and not norm.track_running_stats and norm.running_mean is None else None
+    return None
+
+
+def _form_of(seq):
+    """(form, tensors) of a recognised trunk -- form 'group' or 'batch', the tensors six per block in node_trunk_block
+    order -- or None if `seq` is not `blocks` x the reference's ResBlock(C, C) (stride 1, no downsample, 3x3 / 1 / 1
+    convolutions without bias, no hooks on the blocks) with ONE of the two norms and one eps throughout."""
     blocks = list(seq.children())
     if not blocks:
         return None
     ps = []
     c = None
     eps = None
+    form = None
     for blk in blocks:
         if not isinstance(blk, ResBlock) or blk.downsample is not None or blk._forward_hooks or blk._forward_pre_hooks:
             return None
-        for gn in (blk.norm1, blk.norm2):
-            if not isinstance(gn, nn.GroupNorm) or not gn.affine or gn.num_groups != min(32, gn.num_channels):
+        for norm in (blk.norm1, blk.norm2):
+            f = _norm_form(norm)
+            if f is None:
                 return None
-            c = gn.num_channels if c is None else c
-            eps = gn.eps if eps is None else eps
-            if gn.num_channels != c or gn.eps != eps:
+            nc = norm.num_channels if f == 'group' else norm.num_features
+            form = f if form is None else form
+            c = nc if c is None else c
+            eps = norm.eps if eps is None else eps
+            if f != form or nc != c or norm.eps != eps:
                 return None
         for conv in (blk.conv1, blk.conv2):
             if (conv.kernel_size, conv.stride, conv.padding, conv.dilation, conv.groups, conv.bias, conv.padding_mode) != \
                     ((3, 3), (1, 1), (1, 1), (1, 1), 1, None, 'zeros') or conv.in_channels != c or conv.out_channels != c:
                 return None
         ps += _block_params(blk)
-    return ps
+    return form, ps
+
+
+def _params_of(seq):
+    """The trunk's tensors, six per block in node_trunk_block order, or None if `seq` is not a trunk `_form_of` recognises."""
+    got = _form_of(seq)
+    return None if got is None else got[1]
 
 
 def _struct_array(tensors):
@@ -62,82 +82,126 @@ def _struct_array(tensors):
     return arr
 
 
+class _Entry:
+    """The library calls and the two workspace pools of one trunk node (the workspaces of the two norms have different layouts)."""
+
+    def __init__(self, name):
+        self.bytes, self.fwd, self.bwd = 'node_%s_workspace_bytes' % name, 'node_%s_fwd' % name, 'node_%s_bwd' % name
+        self.free = workspace.Carried()       # (device, shape) -> workspaces whose backward has run: free for the next forward of that shape
+        self.scratch = workspace.Scratch()    # (device, stream, shape) -> the workspace of forwards that keep nothing
+
+
+_GROUP, _BATCH = _Entry('trunk'), _Entry('bntrunk')
+
+
+def _node_forward(entry, ctx, x, eps, want_taps, keep, *params):
+    lib = _lib.load()
+    x = x.detach().contiguous()
+    n, c, h, w = x.shape
+    nblocks = len(params) // 6
+    shape_args = (n, c, h, w, nblocks, eps)
+    shape = _lib.NodeTrunkShape(*shape_args)
+    dev = x.device
+    ps = [p.detach().contiguous() for p in params]
+    with torch.cuda.device(dev):
+        nbytes = getattr(lib, entry.bytes)(C.byref(shape), 1 if keep else 0)
+        if nbytes == 0:
+            _lib.unsupported()
+        if keep:
+            # the workspace carries this forward's activations to its backward: one per forward in flight
+            # (--batch-accumulation, two models: workspace.Carried)
+            key = (dev.index,) + shape_args
+            ws = entry.free.take(key, dev, nbytes)
+        else:
+            ws = entry.scratch.take(dev, nbytes, *shape_args)
+        out = torch.empty_like(x)
+        taps = torch.empty((nblocks,) + tuple(x.shape), dtype=torch.float32, device=dev) if want_taps else None
+        _lib.check(getattr(lib, entry.fwd)(C.byref(shape), _struct_array(ps), x.data_ptr(), out.data_ptr(),
+                                           taps.data_ptr() if want_taps else None, 1 if keep else 0, workspace.aligned_ptr(ws),
+                                           nbytes, torch.cuda.current_stream(dev).cuda_stream))
+    ctx.ws = None
+    if keep:
+        ctx.shape_args, ctx.ws, ctx.nbytes, ctx.key = shape_args, ws, nbytes, key
+        ctx.save_for_backward(*ps)
+    if want_taps:
+        ctx.mark_non_differentiable(taps)
+        return out, taps
+    return out
+
+
+def _node_backward(entry, ctx, grad_out):
+    if ctx.ws is None:
+        raise RuntimeError('the fused trunk keeps its activations in a workspace that the first backward releases: '
+                           'a second backward through the same forward (retain_graph=True) is not supported')
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError('ResidualTrunk: the fused backward does not run inside a stream capture')
+    lib = _lib.load()
+    ps = list(ctx.saved_tensors)
+    shape = _lib.NodeTrunkShape(*ctx.shape_args)
+    dev = ps[0].device
+    grad_out = grad_out.contiguous()
+    if grad_out.dtype != torch.float32:
+        grad_out = grad_out.float()
+    ws = ctx.ws
+    with torch.cuda.device(dev):
+        grads = [torch.empty_like(p) for p in ps]
+        dx = torch.empty_like(grad_out)
+        _lib.check(getattr(lib, entry.bwd)(C.byref(shape), _struct_array(ps), grad_out.data_ptr(), _struct_array(grads),
+                                           dx.data_ptr(), workspace.aligned_ptr(ws), ctx.nbytes,
+                                           torch.cuda.current_stream(dev).cuda_stream))
+    entry.free.give(ctx.key, ws)      # free for the next forward of this shape (stream-ordered behind this backward)
+    ctx.ws = None
+    return (dx, None, None, None, *grads)
+
+
 class _TrunkFn(torch.autograd.Function):
+    """`blocks` x ResBlock(C, C) with GroupNorm: node_trunk_fwd / node_trunk_bwd (csrc/trunk_api.hip)."""
+
     @staticmethod
     def forward(ctx, x, eps, want_taps, keep, *params):
-        lib = _lib.load()
-        x = x.detach().contiguous()
-        n, c, h, w = x.shape
-        nblocks = len(params) // 6
-        shape_args = (n, c, h, w, nblocks, eps)
-        shape = _lib.NodeTrunkShape(*shape_args)
-        dev = x.device
-        ps = [p.detach().contiguous() for p in params]
-        with torch.cuda.device(dev):
-            nbytes = lib.node_trunk_workspace_bytes(C.byref(shape), 1 if keep else 0)
-            if nbytes == 0:
-                _lib.unsupported()
-            if keep:
-                # the workspace carries this forward's activations to its backward: one per forward in flight
-                # (--batch-accumulation, two models: workspace.Carried)
-                key = (dev.index,) + shape_args
-                ws = _FREE.take(key, dev, nbytes)
-            else:
-                ws = _SCRATCH.take(dev, nbytes, *shape_args)
-            out = torch.empty_like(x)
-            taps = torch.empty((nblocks,) + tuple(x.shape), dtype=torch.float32, device=dev) if want_taps else None
-            _lib.check(lib.node_trunk_fwd(C.byref(shape), _struct_array(ps), x.data_ptr(), out.data_ptr(),
-                                          taps.data_ptr() if want_taps else None, 1 if keep else 0, workspace.aligned_ptr(ws),
-                                          nbytes, torch.cuda.current_stream(dev).cuda_stream))
-        if keep:
-            ctx.shape_args, ctx.ws, ctx.nbytes, ctx.key = shape_args, ws, nbytes, key
-            ctx.save_for_backward(*ps)
-        if want_taps:
-            ctx.mark_non_differentiable(taps)
-            return out, taps
-        return out
+        return _node_forward(_GROUP, ctx, x, eps, want_taps, keep, *params)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, grad_out, *unused):
-        if ctx.ws is None:
-            raise RuntimeError('the fused trunk keeps its activations in a workspace that the first backward releases: '
-                               'a second backward through the same forward (retain_graph=True) is not supported')
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError('ResidualTrunk: the fused backward does not run inside a stream capture')
-        lib = _lib.load()
-        ps = list(ctx.saved_tensors)
-        shape = _lib.NodeTrunkShape(*ctx.shape_args)
-        dev = ps[0].device
-        grad_out = grad_out.contiguous()
-        if grad_out.dtype != torch.float32:
-            grad_out = grad_out.float()
-        ws = ctx.ws
-        with torch.cuda.device(dev):
-            grads = [torch.empty_like(p) for p in ps]
-            dx = torch.empty_like(grad_out)
-            _lib.check(lib.node_trunk_bwd(C.byref(shape), _struct_array(ps), grad_out.data_ptr(), _struct_array(grads),
-                                          dx.data_ptr(), workspace.aligned_ptr(ws), ctx.nbytes,
-                                          torch.cuda.current_stream(dev).cuda_stream))
-        _FREE.give(ctx.key, ws)       # free for the next forward of this shape (stream-ordered behind this backward)
-        ctx.ws = None
-        return (dx, None, None, None, *grads)
+        return _node_backward(_GROUP, ctx, grad_out)
+
+
+class _BnTrunkFn(torch.autograd.Function):
+    """The same for `blocks` x ResBlock(C, C, norm='batch'): node_bntrunk_fwd / node_bntrunk_bwd (csrc/bntrunk_api.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, eps, want_taps, keep, *params):
+        return _node_forward(_BATCH, ctx, x, eps, want_taps, keep, *params)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out, *unused):
+        return _node_backward(_BATCH, ctx, grad_out)
 
 
 def fusable(seq, x) -> bool:
-    """What the library's trunk takes (node_trunk_fwd): an fp32 NCHW batch on a HIP device, `blocks` x the reference's
-    ResBlock(C, C) with C a power of two in [64, 4096], images of up to 2400 pixels (the GroupNorm passes hold a (sample,
-    channel block) in LDS), tensors under 2^31 elements, parameters fp32 on the input's device.  Anything else -- the 16-
-    and 32-filter nets of the tests, C = 96, CPU tensors -- runs the module sequence."""
+    """What the library's trunks take (node_trunk_fwd, node_bntrunk_fwd): an fp32 NCHW batch on a HIP device, `blocks` x the
+    reference's ResBlock(C, C), tensors under 2^31 elements, parameters fp32 on the input's device, and
+      GroupNorm: C a power of two in [64, 4096], images of up to 2400 pixels (the passes hold a (sample, channel block) in LDS);
+      BatchNorm (affine, no running statistics; `seq.fused_batch` not switched off): C a multiple of 64 in [64, 4096], more than
+        one value per channel (N H W = 1 is what nn.BatchNorm2d refuses: the modules raise it), 16-byte aligned tensors.
+    Anything else -- the 16- and 32-filter nets of the tests, C = 96, CPU tensors -- runs the module sequence."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[0] >= 1):
         return False
-    ps = _params_of(seq)
-    if ps is None:
+    got = _form_of(seq)
+    if got is None:
         return False
+    form, ps = got
     c = ps[0].shape[0]
     n, cx, h, w = x.shape
-    return (cx == c and 64 <= c <= 4096 and c & (c - 1) == 0 and 1 <= h * w <= 2400 and (n * h * w + 1) * c < 2 ** 31
-            and all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in ps))
+    if not (cx == c and 64 <= c <= 4096 and (n * h * w + 1) * c < 2 ** 31
+            and all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device for p in ps)):
+        return False
+    if form == 'group':
+        return c & (c - 1) == 0 and 1 <= h * w <= 2400
+    return (getattr(seq, 'fused_batch', True) and c % 64 == 0 and n * h * w > 1
+            and all(p.data_ptr() % 16 == 0 for p in ps) and x.data_ptr() % 16 == 0)
 
 
 class ResidualTrunk(nn.Sequential):
@@ -147,7 +211,12 @@ class ResidualTrunk(nn.Sequential):
     in a workspace of its own until its backward has run, so several forwards may be in flight (gradient accumulation)
     and no-grad forwards in between touch none of them.  The first backward releases the workspace: a SECOND backward
     through the same forward (`retain_graph=True`) raises, as the fused stem's does.  A forward under stream capture with
-    gradients wanted, and every input `fusable` refuses, run `nn.Sequential.forward`."""
+    gradients wanted, and every input `fusable` refuses, run `nn.Sequential.forward`.  With `norm='batch'` the node is
+    `_BnTrunkFn` (csrc/bntrunk_api.hip), with the same rules."""
+
+    # norm='batch' trunks as one node of the HIP library (`_BnTrunkFn`); False: the module sequence, as before that node existed
+    # (A/B runs, tests).  GroupNorm trunks do not read it.
+    fused_batch = True
 
     def __init__(self, channels, blocks=6, norm='group'):
         super().__init__(*[ResBlock(channels, channels, norm=norm) for _ in range(blocks)])
@@ -156,11 +225,12 @@ class ResidualTrunk(nn.Sequential):
         return torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in ps))
 
     def _fused(self, x, want_taps):
-        ps = _params_of(self)
+        form, ps = _form_of(self)
         keep = self._wants_grad(x, ps)
         if not keep:
             ps = [p.detach() for p in ps]
-        return _TrunkFn.apply(x, float(self[0].norm1.eps), want_taps, keep, *ps)
+        fn = _TrunkFn if form == 'group' else _BnTrunkFn
+        return fn.apply(x, float(self[0].norm1.eps), want_taps, keep, *ps)
 
     def _takes_fused(self, x):
         return fusable(self, x) and not (self._wants_grad(x, _params_of(self)) and torch.cuda.is_current_stream_capturing())
