@@ -625,6 +625,38 @@ int node_bntrunk_bwd(const node_trunk_shape* shape, const node_trunk_block* bloc
                      const node_trunk_block_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
 int node_bntrunk_describe(const node_trunk_shape* shape, node_bnfunc_info* out);
 
+/* The residual stem with norm = 'batch' -- model.py:167-178 (`ResDownsample`) with model.py:274: the residual stem above in
+ * every respect but the norm, nn.BatchNorm2d(C, track_running_stats=False) (statistics of the batch in training and evaluation
+ * alike) in all four places.  The same shape structure, the same sixteen tensors in the same order (node_stem_params /
+ * node_stem_grads), NCHW at the boundary; the launch plan is the GroupNorm stem's with the BatchNorm passes of the batch-norm
+ * dynamics (two-stage statistics combined by Chan's formula, fp64 backward partials) in place of the GroupNorm passes.  The
+ * last convolution stays on the gather GEMM (the F(4x4,3x3) route of the GroupNorm stem has GroupNorm inside its passes):
+ * NODE_TUNE_STEM_W4 has no effect on this node.
+ *   in_ch <= 3; h, w >= 5 and (h - 2)(w - 2) <= 2400 (the GroupNorm stem's image limit is kept: the first layer's kernels have
+ *   not run above it); filters a multiple of 64 in [64, 4096] (192 and 384 are fine: BatchNorm has no groups); tensors under
+ *   2^31 elements; n h2 w2 > 1 (nn.BatchNorm2d refuses one value per channel).  Anything else: NODE_ERR_UNSUPPORTED with a
+ *   message, and the workspace-size call returns 0.  Every tensor 16-byte aligned (NODE_ERR_ARG), the workspace 256-byte aligned.
+ * keep_for_backward = 0 is the no-grad forward: activations whose lives do not overlap share storage.  The backward needs the
+ * workspace exactly as the forward left it with keep_for_backward = 1 (one workspace per forward in flight).  It writes (does
+ * not accumulate) what is asked for: grads (NULL: frozen parameters -- only the data-gradient chain runs: no weight-gradient
+ * and no slab-reduction launch), d_x [n, in_ch, h, w] (NULL: no image gradient -- the transposed first layer is left out); both
+ * NULL: NODE_ERR_NULL.  d_x is the same bits with and without grads.  The gradient of conv0's bias in front of a BatchNorm is
+ * zero identically: conv0_b receives the computed sum, rounding noise around zero.  No floating-point atomics: every sum runs
+ * in a fixed order, so results are bit-reproducible run to run.  The calls never synchronise, allocate device memory or read
+ * back; refused shapes, NULL and misaligned arguments and a short workspace are rejected before any launch.
+ * The BatchNorm passes' chunks follow a policy of this node's own: at most NODE_TUNE_BNSTEM_MAXCHUNK chunks per 64-channel
+ * tensor (read once per call; unset or 0: the built-in 128, the policy of the other batch-norm nodes).  It is part of the
+ * workspace layout: a backward must run under the value its forward ran under.
+ * The describe call (host only, needs no GPU) fills one node_bnfunc_info per norm, in the order of the tensors they normalise --
+ * h0 (block 1 norm1), h1 (block 1 norm2), x1 (block 2 norm1), h3 (block 2 norm2): rows, chunks and column tiles of that tensor,
+ * wgrad_nsplit / wgrad_rows_per_split of the convolution that reads the norm's output. */
+size_t node_bnstem_workspace_bytes(const node_stem_shape* shape, int keep_for_backward);
+int node_bnstem_describe(const node_stem_shape* shape, node_bnfunc_info out[4]);
+int node_bnstem_fwd(const node_stem_shape* shape, const node_stem_params* params, const float* x, float* out,
+                    int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_bnstem_bwd(const node_stem_shape* shape, const node_stem_params* params, const float* x, const float* grad_out,
+                    const node_stem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
 /* Classifier head of a norm = 'batch' net, up to (not including) the Linear layer -- model.py:231-250 with model.py:274:
  * BatchNorm2d(channels, track_running_stats=False) -> ReLU -> AdaptiveAvgPool2d((1,1)) -> [Dropout] -> Flatten:
  *     pooled[n, c] = scale[n, c] * mean over pixels of relu(gamma[c] * xhat + beta[c])

@@ -55,6 +55,7 @@ EXPORTS = [
     'node_bnsolve_workspace_bytes', 'node_bnsolve_fwd', 'node_bnsolve_adjoint',
     'node_bntrunk_workspace_bytes', 'node_bntrunk_fwd', 'node_bntrunk_bwd', 'node_bntrunk_describe',
     'node_bnhead_scratch_bytes', 'node_bnhead_fwd', 'node_bnhead_bwd',
+    'node_bnstem_workspace_bytes', 'node_bnstem_describe', 'node_bnstem_fwd', 'node_bnstem_bwd',
 ]
 
 
@@ -186,6 +187,14 @@ def describe_bntrunk(n, c, h, w, blocks=6, eps=1e-5):
     info = NodeBnfuncInfo()
     check(load().node_bntrunk_describe(C.byref(NodeTrunkShape(n, c, h, w, blocks, eps)), C.byref(info)))
     return {k: getattr(info, k) for k, _ in info._fields_}
+
+
+def bnstem_plan(n, in_ch, h, w, filters, eps=1e-5):
+    """The launch plan of the `norm='batch'` residual stem for an [n, in_ch, h, w] batch: four dicts of node_bnfunc_info, one per
+    norm (block 1 norm1, norm2, block 2 norm1, norm2).  Needs no GPU; raises NodeHipError for a shape the node refuses."""
+    info = (NodeBnfuncInfo * 4)()
+    check(load().node_bnstem_describe(C.byref(NodeStemShape(n, in_ch, h, w, filters, eps)), info))
+    return [{k: getattr(i, k) for k, _ in i._fields_} for i in info]
 
 
 class NodeBnsolveOpts(C.Structure):
@@ -472,6 +481,14 @@ def load():
     lib.node_bntrunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
     lib.node_bntrunk_describe.restype = i32
     lib.node_bntrunk_describe.argtypes = [P(NodeTrunkShape), P(NodeBnfuncInfo)]
+    lib.node_bnstem_workspace_bytes.restype = sz
+    lib.node_bnstem_workspace_bytes.argtypes = [P(NodeStemShape), i32]
+    lib.node_bnstem_describe.restype = i32
+    lib.node_bnstem_describe.argtypes = [P(NodeStemShape), P(NodeBnfuncInfo)]
+    lib.node_bnstem_fwd.restype = i32
+    lib.node_bnstem_fwd.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, i32, vp, sz, vp]
+    lib.node_bnstem_bwd.restype = i32
+    lib.node_bnstem_bwd.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, P(NodeStemParams), vp, vp, sz, vp]
     lib.node_bnhead_scratch_bytes.restype = sz
     lib.node_bnhead_scratch_bytes.argtypes = [P(NodeBnfuncShape)]
     lib.node_bnhead_fwd.restype = i32
