@@ -783,6 +783,68 @@ int node_convstem_bwd(const node_convstem_shape* shape, const node_convstem_para
 int node_convstem_bwd_dx(const node_convstem_shape* shape, const node_convstem_params* params, const float* x, const float* grad_out,
                          const node_convstem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
 
+/* The `convolution` stem with norm = 'batch' -- model.py:148-164 with model.py:274: the stem above in every respect but the
+ * norm, nn.BatchNorm2d(64, track_running_stats=False) (statistics of the batch in training and evaluation alike) in both
+ * places.  The same shape structure and the same ten tensors in the same order (node_convstem_params / node_convstem_grads,
+ * n1_* / n2_* holding the BatchNorms' weight and bias), NCHW at the boundary; the launch plan is the GroupNorm stem's with the
+ * BatchNorm passes of the batch-norm dynamics (two-stage statistics combined by Chan's formula, fp64 backward partials) in place
+ * of the GroupNorm passes.
+ *   in_ch <= 3; h, w >= 10 and (h - 2)(w - 2) <= 2400 (the GroupNorm stem's image limit is kept: the first layer's kernels have
+ *   not run above it); filters a multiple of 64 in [64, 4096] (192 and 384 are fine: BatchNorm has no groups); tensors under
+ *   2^31 elements.  Anything else: NODE_ERR_SHAPE / NODE_ERR_UNSUPPORTED with a message, and the workspace-size call returns 0.
+ *   Every tensor 16-byte aligned (NODE_ERR_ARG), the workspace 256-byte aligned.
+ * keep_for_backward = 0 is the no-grad forward: tensors whose lives do not overlap share storage.  The backward calls need the
+ * workspace exactly as the forward left it with keep_for_backward = 1 (one workspace per forward in flight).  node_bnconvstem_bwd
+ * writes (does not accumulate) all ten parameter gradients (grads required); node_bnconvstem_bwd_dx also the image's gradient
+ * d_x [n, in_ch, h, w] (required), and with grads == NULL (frozen parameters) runs the data-gradient chain alone: no
+ * weight-gradient, partial-sum or reduction launch.  d_x is the same bits with and without grads, the parameter gradients the
+ * same bits from either call.  The biases of the first two convolutions stand in front of a BatchNorm, so their gradients are
+ * zero identically: c0_b and c1_b receive the computed sums, rounding noise around zero.  No floating-point atomics: every
+ * sum runs in a fixed order, so results are bit-reproducible run to run.  The calls never synchronise, allocate device memory
+ * or read back; refused shapes, NULL and misaligned arguments and a short workspace are rejected before any launch.
+ * The BatchNorm passes' chunks follow the batch-norm residual stem's policy (NODE_TUNE_BNSTEM_MAXCHUNK, part of the workspace
+ * layout).  The describe call (host only, needs no GPU) fills one node_bnfunc_info per norm -- h0 (behind the first
+ * convolution), h1 (behind the middle one): rows, chunks and column tiles of that tensor, wgrad_nsplit /
+ * wgrad_rows_per_split of the convolution that reads the norm's output. */
+size_t node_bnconvstem_workspace_bytes(const node_convstem_shape* shape, int keep_for_backward);
+int node_bnconvstem_describe(const node_convstem_shape* shape, node_bnfunc_info out[2]);
+int node_bnconvstem_fwd(const node_convstem_shape* shape, const node_convstem_params* params, const float* x, float* out,
+                        int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_bnconvstem_bwd(const node_convstem_shape* shape, const node_convstem_params* params, const float* x, const float* grad_out,
+                        const node_convstem_grads* grads, void* ws, size_t ws_bytes, void* stream);
+int node_bnconvstem_bwd_dx(const node_convstem_shape* shape, const node_convstem_params* params, const float* x,
+                           const float* grad_out, const node_convstem_grads* grads, float* d_x, void* ws, size_t ws_bytes,
+                           void* stream);
+
+/* The `ode2` stem's hand-off with norm = 'batch' -- model.py:199-223 with model.py:274:
+ *     y = conv(relu(norm(x))),   norm = nn.BatchNorm2d(cin, track_running_stats=False),   conv = nn.Conv2d(cin, cout, 4, 2, 1) with bias
+ * node_downconv_*'s plan with the BatchNorm passes; node_downconv_params / node_downconv_grads with gn_w / gn_b holding the
+ * BatchNorm's weight and bias.  x, d_x: [n, cin, h, w]; y, grad_y: [n, cout, oh, ow], NCHW fp32.
+ *   slices: 1, or T > 1: n = T * (n / T) samples are T slices of a trajectory [T, n / T, cin, h, w], each normalised with its own
+ *   statistics (model.py:214-216 sends a trajectory through the norm slice by slice) -- one call instead of T, and every slice
+ *   the bits of its own slices = 1 call.  Forward with keep_for_backward = 0 only: node_bndownconv_workspace_bytes(shape, 1)
+ *   returns 0 with a message and node_bndownconv_fwd(.., keep_for_backward = 1, ..) / node_bndownconv_bwd return
+ *   NODE_ERR_UNSUPPORTED for slices > 1 (feature extraction runs without gradients).
+ *   cin, cout multiples of 64 in [64, 4096] (192 is fine); h, w >= 4 (no upper limit: the BatchNorm passes hold no image);
+ *   slices >= 1 and n % slices == 0 (NODE_ERR_SHAPE); tensors under 2^31 elements.  Anything else: NODE_ERR_UNSUPPORTED with a
+ *   message; the workspace-size call returns 0 with the same message.  Every tensor 16-byte aligned (NODE_ERR_ARG), the
+ *   workspace 256-byte aligned.
+ * node_bndownconv_bwd writes (does not accumulate) d_x (required) and, with grads given (NULL: the input gradient only -- no
+ * weight-gradient and no reduction launch), all four parameter gradients.  No floating-point atomics; the same bits on every
+ * run.  The calls never synchronise, allocate device memory or read back; everything refused is refused before any launch.
+ * The describe call (host only, needs no GPU): rows = n h w, chunk_rows (what ONE slice's plan takes), nchunk = slices x chunks
+ * per slice, last_chunk_rows = the last chunk's of every slice, column_tiles = cin / 64, the weight gradient's split. */
+typedef struct node_bndownconv_shape {
+  int32_t n, cin, cout, h, w, slices;
+  float eps;
+} node_bndownconv_shape;
+size_t node_bndownconv_workspace_bytes(const node_bndownconv_shape* shape, int keep_for_backward);
+int node_bndownconv_describe(const node_bndownconv_shape* shape, node_bnfunc_info* out);
+int node_bndownconv_fwd(const node_bndownconv_shape* shape, const node_downconv_params* params, const float* x, float* y,
+                        int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_bndownconv_bwd(const node_bndownconv_shape* shape, const node_downconv_params* params, const float* grad_y,
+                        const node_downconv_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
 /* The `minimal` stem in front of the ODE block -- model.py:129-145 (`MinimalConvDownsample`):
  *     Conv2d(in_ch, 24, 3, 1) | GroupNorm(24, 24) + ReLU | Conv2d(24, 24, 4, 2, 1) | GroupNorm(24, 24) + ReLU |
  *     Conv2d(24, filters, 4, 2, 1),  every convolution with bias

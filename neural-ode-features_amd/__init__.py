@@ -15,7 +15,7 @@ from .augment import Augmenter, DeviceSplit, TransferTransform  # noqa: F401
 from .imgconv import ImageConv2d  # noqa: F401
 from .convstem import ConvStem  # noqa: F401
 from .ministem import MinimalStem  # noqa: F401
-from .downconv import gn_relu_conv  # noqa: F401
+from .downconv import bn_relu_conv, gn_relu_conv  # noqa: F401
 from .pool import max_pool_4s2, trajectory_pool  # noqa: F401
 from .resnet import ResNet, ResidualTrunk, build_model  # noqa: F401
 from .optim import FusedAdam, FusedSGD  # noqa: F401

@@ -56,6 +56,8 @@ EXPORTS = [
     'node_bntrunk_workspace_bytes', 'node_bntrunk_fwd', 'node_bntrunk_bwd', 'node_bntrunk_describe',
     'node_bnhead_scratch_bytes', 'node_bnhead_fwd', 'node_bnhead_bwd',
     'node_bnstem_workspace_bytes', 'node_bnstem_describe', 'node_bnstem_fwd', 'node_bnstem_bwd',
+    'node_bnconvstem_workspace_bytes', 'node_bnconvstem_describe', 'node_bnconvstem_fwd', 'node_bnconvstem_bwd', 'node_bnconvstem_bwd_dx',
+    'node_bndownconv_workspace_bytes', 'node_bndownconv_describe', 'node_bndownconv_fwd', 'node_bndownconv_bwd',
 ]
 
 
@@ -222,6 +224,28 @@ class NodeConvStemShape(C.Structure):
 
 class NodeConvStemParams(C.Structure):      # node_convstem_params and node_convstem_grads share this layout
     _fields_ = [(k, C.c_void_p) for k in CONVSTEM_PARAM_FIELDS]
+
+
+class NodeBnDownConvShape(C.Structure):
+    _fields_ = [('n', C.c_int32), ('cin', C.c_int32), ('cout', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('slices', C.c_int32),
+                ('eps', C.c_float)]
+
+
+def bnconvstem_plan(n, in_ch, h, w, filters, eps=1e-5):
+    """The launch plan of the `norm='batch'` convolution stem for an [n, in_ch, h, w] batch: two dicts of node_bnfunc_info, one per
+    norm (behind the first convolution, behind the middle one).  Needs no GPU; raises NodeHipError for a shape the node refuses."""
+    info = (NodeBnfuncInfo * 2)()
+    check(load().node_bnconvstem_describe(C.byref(NodeConvStemShape(n, in_ch, h, w, filters, eps)), info))
+    return [{k: getattr(i, k) for k, _ in i._fields_} for i in info]
+
+
+def describe_bndownconv(n, cin, cout, h, w, slices=1, eps=1e-5):
+    """The launch plan of the `norm='batch'` hand-off for an [n, cin, h, w] batch of `slices` slices: dict of node_bnfunc_info
+    (chunk_rows: what one slice's plan takes; nchunk = slices x chunks per slice; last_chunk_rows: the last chunk's of every slice).
+    Needs no GPU; raises NodeHipError for a shape the node refuses."""
+    info = NodeBnfuncInfo()
+    check(load().node_bndownconv_describe(C.byref(NodeBnDownConvShape(n, cin, cout, h, w, slices, eps)), C.byref(info)))
+    return {k: getattr(info, k) for k, _ in info._fields_}
 
 
 class NodeMiniStemShape(C.Structure):
@@ -509,6 +533,24 @@ def load():
     lib.node_convstem_bwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, sz, vp]
     lib.node_convstem_bwd_dx.restype = i32
     lib.node_convstem_bwd_dx.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, vp, sz, vp]
+    lib.node_bnconvstem_workspace_bytes.restype = sz
+    lib.node_bnconvstem_workspace_bytes.argtypes = [P(NodeConvStemShape), i32]
+    lib.node_bnconvstem_describe.restype = i32
+    lib.node_bnconvstem_describe.argtypes = [P(NodeConvStemShape), P(NodeBnfuncInfo)]
+    lib.node_bnconvstem_fwd.restype = i32
+    lib.node_bnconvstem_fwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, i32, vp, sz, vp]
+    lib.node_bnconvstem_bwd.restype = i32
+    lib.node_bnconvstem_bwd.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, sz, vp]
+    lib.node_bnconvstem_bwd_dx.restype = i32
+    lib.node_bnconvstem_bwd_dx.argtypes = [P(NodeConvStemShape), P(NodeConvStemParams), vp, vp, P(NodeConvStemParams), vp, vp, sz, vp]
+    lib.node_bndownconv_workspace_bytes.restype = sz
+    lib.node_bndownconv_workspace_bytes.argtypes = [P(NodeBnDownConvShape), i32]
+    lib.node_bndownconv_describe.restype = i32
+    lib.node_bndownconv_describe.argtypes = [P(NodeBnDownConvShape), P(NodeBnfuncInfo)]
+    lib.node_bndownconv_fwd.restype = i32
+    lib.node_bndownconv_fwd.argtypes = [P(NodeBnDownConvShape), P(NodeDownConvParams), vp, vp, i32, vp, sz, vp]
+    lib.node_bndownconv_bwd.restype = i32
+    lib.node_bndownconv_bwd.argtypes = [P(NodeBnDownConvShape), P(NodeDownConvParams), vp, P(NodeDownConvParams), vp, vp, sz, vp]
     lib.node_ministem_workspace_bytes.restype = sz
     lib.node_ministem_workspace_bytes.argtypes = [P(NodeMiniStemShape), i32]
     lib.node_ministem_fwd.restype = i32

@@ -6,6 +6,10 @@ PyTorch reductions.  `ConvStem` IS the reference's `nn.Sequential` of seven chil
 `1.weight`, `3.weight`, ...), so checkpoints load unchanged; CPU tensors, non-fp32 inputs, an input that requires a gradient
 (unless `ConvStem.input_grad` is on: node_convstem_bwd_dx then returns the image's gradient too), a stream that is being captured
 and shapes the kernels refuse run the module sequence -- on a HIP device with the library missing, the fused path raises.
+
+A `norm='batch'` stem (both norms `nn.BatchNorm2d(64, track_running_stats=False)`, model.py:274) is one node too:
+`_BnConvStemFn` (`node_bnconvstem_fwd / _bwd / _bwd_dx`, csrc/bnconvstem_api.hip), the same launch plan around the BatchNorm
+passes of the batch-norm dynamics; filters may be any multiple of 64.  `ConvStem.fused_batch = False` runs its module sequence.
 """
 from __future__ import annotations
 
@@ -13,6 +17,7 @@ import ctypes as C
 
 import torch
 from torch import nn
+from torch.autograd.function import once_differentiable
 
 from . import _lib, workspace
 
@@ -128,6 +133,145 @@ def fusable(seq, x, input_grad=False) -> bool:
     return _lib.load().node_convstem_workspace_bytes(C.byref(shape), 1) != 0      # (0: refused, with a message)
 
 
+def _bn_params_of(seq):
+    """The same ten tensors for a `norm='batch'` stem, or None: the reference's layout with two
+    `nn.BatchNorm2d(64, track_running_stats=False)` (model.py:274) -- affine, no running buffers (they would have to be updated in
+    training and USED in evaluation: the node does neither), one eps -- and the convolution geometry `_params_of` asks for."""
+    try:
+        c0, n1, r1, c1, n2, r2, c2 = list(seq.children())
+    except ValueError:
+        return None
+    if not (isinstance(r1, nn.ReLU) and isinstance(r2, nn.ReLU)):
+        return None
+    for conv, geom in ((c0, ((3, 3), (1, 1), (0, 0))), (c1, ((4, 4), (2, 2), (1, 1))), (c2, ((4, 4), (2, 2), (1, 1)))):
+        if not isinstance(conv, nn.Conv2d) or conv.bias is None:
+            return None
+        if (conv.kernel_size, conv.stride, conv.padding) != geom or (conv.dilation, conv.groups, conv.padding_mode) != ((1, 1), 1, 'zeros'):
+            return None
+    for bn in (n1, n2):
+        if not isinstance(bn, nn.BatchNorm2d) or not bn.affine or bn.track_running_stats or bn.running_mean is not None \
+                or bn.eps != n1.eps or bn.num_features != 64:
+            return None
+    if (c0.out_channels, c1.in_channels, c1.out_channels, c2.in_channels) != (64, 64, 64, 64):
+        return None
+    return [c0.weight, c0.bias, n1.weight, n1.bias, c1.weight, c1.bias, n2.weight, n2.bias, c2.weight, c2.bias]
+
+
+def _out_size(h):
+    return ((h - 2 - 2) // 2 + 1 - 2) // 2 + 1
+
+
+_BN_FREE = workspace.Carried()       # (device, shape) -> workspaces whose backward has run: free for the next forward of that shape
+_BN_SCRATCH = workspace.Scratch()    # (device, stream, shape) -> the workspace of forwards that keep nothing
+
+
+class _BnConvStemFn(torch.autograd.Function):
+    """The `norm='batch'` convolution stem: node_bnconvstem_fwd / _bwd / _bwd_dx (csrc/bnconvstem_api.hip), with `stem._BnStemFn`'s
+    workspace discipline: a forward that wants gradients keeps its activations in a workspace of its own until its backward has
+    run, a no-grad forward uses the stream's scratch and touches none of them."""
+
+    @staticmethod
+    def forward(ctx, x, eps, keep, *params):
+        lib = _lib.load()
+        x = x.detach().contiguous()
+        n, cin, h, w = x.shape
+        filters = params[-1].shape[0]
+        shape_args = (n, cin, h, w, filters, eps)
+        shape = _lib.NodeConvStemShape(*shape_args)
+        dev = x.device
+        ps = [p.detach().contiguous() for p in params]
+        with torch.cuda.device(dev):
+            nbytes = lib.node_bnconvstem_workspace_bytes(C.byref(shape), 1 if keep else 0)
+            if nbytes == 0:
+                _lib.unsupported()
+            if keep:
+                key = (dev.index,) + shape_args
+                ws = _BN_FREE.take(key, dev, nbytes)
+            else:
+                ws = _BN_SCRATCH.take(dev, nbytes, *shape_args)
+            out = torch.empty(n, filters, _out_size(h), _out_size(w), dtype=torch.float32, device=dev)
+            _lib.check(lib.node_bnconvstem_fwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), out.data_ptr(), 1 if keep else 0,
+                                               workspace.aligned_ptr(ws), nbytes, torch.cuda.current_stream(dev).cuda_stream))
+        ctx.ws = None
+        if keep:
+            ctx.shape_args, ctx.ws, ctx.nbytes, ctx.key = shape_args, ws, nbytes, key
+            ctx.save_for_backward(x, *ps)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        if ctx.ws is None:
+            raise RuntimeError('the fused stem keeps its activations in a workspace that the first backward releases: '
+                               'a second backward through the same forward (retain_graph=True) is not supported')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ConvStem: the fused backward does not run inside a stream capture')
+        lib = _lib.load()
+        x, *ps = ctx.saved_tensors
+        shape = _lib.NodeConvStemShape(*ctx.shape_args)
+        dev = x.device
+        grad_out = grad_out.contiguous()
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        if grad_out.data_ptr() % 16:
+            grad_out = grad_out.clone()
+        # parameter gradients: all ten or none (an attack freezes the parameters: the data-gradient chain alone)
+        want_params = any(ctx.needs_input_grad[3:])
+        want_dx = ctx.needs_input_grad[0]     # (only with ConvStem.input_grad: `bn_fusable` sends any other such input elsewhere)
+        ws = ctx.ws
+        with torch.cuda.device(dev):
+            grads = [torch.empty_like(p) for p in ps] if want_params or not want_dx else None
+            d_x = torch.empty_like(x) if want_dx else None
+            wsp = workspace.aligned_ptr(ws)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if want_dx:
+                _lib.check(lib.node_bnconvstem_bwd_dx(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                                      C.byref(_struct(grads)) if grads is not None else None, d_x.data_ptr(), wsp,
+                                                      ctx.nbytes, stream))
+            else:
+                _lib.check(lib.node_bnconvstem_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                                   C.byref(_struct(grads)), wsp, ctx.nbytes, stream))
+        _BN_FREE.give(ctx.key, ws)       # free for the next forward of this shape (stream-ordered behind this backward)
+        ctx.ws = None
+        if grads is None:
+            grads = [None] * len(ps)
+        return (d_x, None, None, *grads)
+
+
+def _hooked(seq):
+    """a forward or backward hook on one of the stem's sub-modules: the node would not call it (hooks on the stem itself run)"""
+    return any(m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, '_backward_pre_hooks', None)
+               for m in seq.modules() if m is not seq)
+
+
+def _is_batch(seq):
+    """the first norm is a BatchNorm2d (one look, so that GroupNorm stems pay nothing for the other node)"""
+    return len(seq) > 1 and isinstance(seq[1], nn.BatchNorm2d)
+
+
+def bn_fusable(seq, x, input_grad=False) -> bool:
+    """What node_bnconvstem_fwd takes: an fp32 NCHW batch on a HIP device with in_ch <= 3, h, w >= 10 and up to 2400 pixels behind
+    the first layer; a stem `_bn_params_of` recognises, filters a multiple of 64 in [64, 4096] (192 and 384 included), fp32
+    parameters on the input's device, 16-byte aligned tensors under 2^31 elements, no hooks on the stem's sub-modules; an input
+    that requires a gradient only with `input_grad`; no stream capture.  Anything else runs the module sequence."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and 1 <= x.shape[1] <= 3 and x.shape[0] >= 1
+            and min(x.shape[2], x.shape[3]) >= 10 and (x.shape[2] - 2) * (x.shape[3] - 2) <= 2400):
+        return False
+    ps = _bn_params_of(seq)
+    if ps is None or _hooked(seq):
+        return False
+    if x.requires_grad and torch.is_grad_enabled() and not input_grad:
+        return False
+    n, cin, h, w = x.shape
+    filters = ps[-1].shape[0]
+    if not (filters % 64 == 0 and 64 <= filters <= 4096 and ps[0].shape[1] == cin
+            and n * (h - 2) * (w - 2) * 64 + 4096 < 2 ** 31 and n * h * w * filters < 2 ** 31):
+        return False
+    if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device and p.data_ptr() % 16 == 0 for p in ps):
+        return False
+    return x.data_ptr() % 16 == 0 and not torch.cuda.is_current_stream_capturing()
+
+
 class ConvStem(nn.Sequential):
     """`nn.Sequential(Conv2d(in_ch, 64, 3, 1), GN, ReLU, Conv2d(64, 64, 4, 2, 1), GN, ReLU, Conv2d(64, out_ch, 4, 2, 1))` with
     the reference's state_dict keys; on a HIP device its forward and backward are the library's (one autograd node).
@@ -137,8 +281,20 @@ class ConvStem(nn.Sequential):
     an input runs the module sequence, as it always has.  `nof.attack.bim` switches it on for the attack's duration."""
 
     input_grad = False
+    # norm='batch' stems as one node of the HIP library (`_BnConvStemFn`, csrc/bnconvstem_api.hip); False: the module sequence, as
+    # before that node existed (A/B runs, tests).  GroupNorm stems do not read it.  `eval()` changes nothing: without running
+    # statistics the reference normalises with the batch's statistics in evaluation too.
+    fused_batch = True
 
     def forward(self, x):
+        if _is_batch(self):
+            if not (self.fused_batch and bn_fusable(self, x, self.input_grad)):
+                return super().forward(x)
+            ps = _bn_params_of(self)
+            keep = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in ps))
+            if not keep:
+                ps = [p.detach() for p in ps]
+            return _BnConvStemFn.apply(x, float(self[1].eps), keep, *ps)
         if not fusable(self, x, self.input_grad):
             return super().forward(x)
         ps = _params_of(self)

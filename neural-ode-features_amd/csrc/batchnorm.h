@@ -46,9 +46,20 @@ struct SBnArgs {
   float da_scale = 1.0f;   // on every read of `da` in the two backward passes
   // the residual trunk (bntrunk_api.hip): h also is the block's shortcut, so its gradient is du + skip.  Not with clsp.
   const float* skip = nullptr;   // nullable fp32 NHWC, added to du before the fp32 store and the triple split (dx pass only)
+  // slices (bndownconv_api.hip; the two forward passes only): rows = slices * rows_per_slice, statistics per (slice, channel).  Chunks
+  // never straddle a slice: nchunk = slices * chunks_per_slice, chunk slice * chunks_per_slice + k starts at row slice * rows_per_slice +
+  // k * chunk_rows (any row: not a multiple of 32 or of chunk_rows in general), the last chunk of every slice may be short; part stays
+  // [nchunk][2][C], stats becomes [slices][2][C].  With chunk_rows what one slice alone would take, every slice has the bits of its
+  // own unsliced call.  0 or 1: the unsliced passes, which read neither of the other two.
+  int slices = 1;
+  int rows_per_slice = 0;
+  int chunks_per_slice = 0;
 };
 // rows per chunk for a tensor of `rows` x C: <= 128 chunks, enough (chunk, channel block) pairs to cover the device
 int bn_chunk_rows(int rows, int C);
+// the same for a tensor of the stems (bnstem_api.hip): at most NODE_TUNE_BNSTEM_MAXCHUNK chunks at C = 64 (unset or 0: 128, at which
+// it is bn_chunk_rows)
+int bnstem_chunk_rows(int rows, int C);
 void launch_bn_stats(const SBnArgs& a, hipStream_t s);
 void launch_bn_apply(const SBnArgs& a, hipStream_t s);
 void launch_bn_bwd_stats(const SBnArgs& a, hipStream_t s);

@@ -120,7 +120,12 @@ __device__ __forceinline__ double colsum64d(const float (&s)[8], float* red, int
   return r;
 }
 
-struct Geo { int chunk, c0, c, r0, r1, rr; };
+// sl, k: the chunk's slice and its index inside the slice (SLICED; otherwise 0 and the chunk itself)
+struct Geo { int chunk, c0, c, r0, r1, rr, sl, k; };
+// SLICED (batchnorm.h): chunks never straddle a slice -- chunk = slice * chunks_per_slice + k covers the rows
+// slice * rows_per_slice + k * chunk_rows .. of its own slice only, the last one of every slice possibly short.  A variant at compile
+// time, so the unsliced instances every other node launches keep their instruction streams.
+template <bool SLICED = false>
 __device__ __forceinline__ Geo bn_geo(const SBnArgs& a) {
   Geo g;
   const int nct = a.C >> 6, t = threadIdx.x;
@@ -128,19 +133,30 @@ __device__ __forceinline__ Geo bn_geo(const SBnArgs& a) {
   g.c0 = (blockIdx.x - g.chunk * nct) << 6;
   g.c = g.c0 + 8 * (t & 7);
   g.rr = t >> 3;
-  g.r0 = g.chunk * a.chunk_rows;
-  g.r1 = min(g.r0 + a.chunk_rows, a.rows);
+  if constexpr (SLICED) {
+    g.sl = g.chunk / a.chunks_per_slice;
+    g.k = g.chunk - g.sl * a.chunks_per_slice;
+    const int s0 = g.sl * a.rows_per_slice;
+    g.r0 = s0 + g.k * a.chunk_rows;
+    g.r1 = min(g.r0 + a.chunk_rows, s0 + a.rows_per_slice);
+  } else {
+    g.sl = 0;
+    g.k = g.chunk;
+    g.r0 = g.chunk * a.chunk_rows;
+    g.r1 = min(g.r0 + a.chunk_rows, a.rows);
+  }
   return g;
 }
 
 // ============================================================================
 // forward, stage 1: per (chunk, channel) the chunk's mean and centred second moment
 // ============================================================================
+template <bool SLICED>
 __global__ __launch_bounds__(256) void k_bn_stats(const SBnArgs a) {
   __shared__ __align__(16) float red[32 * 64];
   __shared__ float cm[64];
   const int t = threadIdx.x;
-  const Geo g = bn_geo(a);
+  const Geo g = bn_geo<SLICED>(a);
   const float tv = a.T != nullptr ? *a.t : 0.f;
   float s[8];
 #pragma unroll
@@ -183,12 +199,17 @@ __device__ __forceinline__ void chan_merge(float& n, float& m, float& M2, float 
 }
 // the batch statistics of the workgroup's 64 channels from the partials: thread (c = t % 64, q = t / 64) merges chunks q, q + 4, ..,
 // thread c then the four chains in order.  sm: [4][3][64].  mean, rstd: [64], valid behind the closing barrier.
-__device__ __forceinline__ void bn_combine(const SBnArgs& a, int c0, float* sm, float* mean, float* rstd, int t) {
+// SLICED: only the chunks_per_slice partials of slice `sl`, in the same order, over rows_per_slice rows: what an unsliced call on
+// that slice alone combines, so the same bits.
+template <bool SLICED>
+__device__ __forceinline__ void bn_combine(const SBnArgs& a, int c0, int sl, float* sm, float* mean, float* rstd, int t) {
   const int c = t & 63, q = t >> 6;
+  const int nk_all = SLICED ? a.chunks_per_slice : a.nchunk, rows = SLICED ? a.rows_per_slice : a.rows;
+  const float* part = SLICED ? a.part + (size_t)sl * a.chunks_per_slice * 2 * a.C : a.part;
   float n = 0.f, m = 0.f, M2 = 0.f;
-  for (int k = q; k < a.nchunk; k += 4) {
-    const float nk = (float)min(a.chunk_rows, a.rows - k * a.chunk_rows);
-    chan_merge(n, m, M2, nk, a.part[((size_t)k * 2 + 0) * a.C + c0 + c], a.part[((size_t)k * 2 + 1) * a.C + c0 + c]);
+  for (int k = q; k < nk_all; k += 4) {
+    const float nk = (float)min(a.chunk_rows, rows - k * a.chunk_rows);
+    chan_merge(n, m, M2, nk, part[((size_t)k * 2 + 0) * a.C + c0 + c], part[((size_t)k * 2 + 1) * a.C + c0 + c]);
   }
   sm[(q * 3 + 0) * 64 + c] = n;
   sm[(q * 3 + 1) * 64 + c] = m;
@@ -202,7 +223,7 @@ __device__ __forceinline__ void bn_combine(const SBnArgs& a, int c0, float* sm, 
       if (nj > 0.f) chan_merge(n, m, M2, nj, sm[(j * 3 + 1) * 64 + t], sm[(j * 3 + 2) * 64 + t]);     // (fewer than four chunks: a shape's property, not the data's)
     }
     mean[t] = m;
-    rstd[t] = 1.f / sqrtf(M2 / (float)a.rows + a.eps);
+    rstd[t] = 1.f / sqrtf(M2 / (float)rows + a.eps);
   }
   __syncthreads();
 }
@@ -210,15 +231,17 @@ __device__ __forceinline__ void bn_combine(const SBnArgs& a, int c0, float* sm, 
 // ============================================================================
 // forward, stage 2: y = [relu](xhat gamma + beta) as triples and / or fp32
 // ============================================================================
+template <bool SLICED>
 __global__ __launch_bounds__(256) void k_bn_apply(const SBnArgs a) {
   __shared__ float sm[4 * 3 * 64];
   __shared__ float smean[64], srstd[64];
   const int t = threadIdx.x;
-  const Geo g = bn_geo(a);
-  bn_combine(a, g.c0, sm, smean, srstd, t);
-  if (g.chunk == 0 && t < 64) {
-    a.stats[g.c0 + t] = smean[t];
-    a.stats[a.C + g.c0 + t] = srstd[t];
+  const Geo g = bn_geo<SLICED>(a);
+  bn_combine<SLICED>(a, g.c0, g.sl, sm, smean, srstd, t);
+  if (g.k == 0 && t < 64) {      // the first chunk of the slice: stats [slices][2][C]
+    float* st = SLICED ? a.stats + (size_t)g.sl * 2 * a.C : a.stats;
+    st[g.c0 + t] = smean[t];
+    st[a.C + g.c0 + t] = srstd[t];
   }
   const float tv = a.T != nullptr ? *a.t : 0.f;
   float mu[8], rs[8], ga[8], be[8];
@@ -591,8 +614,15 @@ int bn_chunk_rows(int rows, int C) {
 }
 static dim3 bn_grid(const SBnArgs& a) { return dim3((unsigned)(a.nchunk * (a.C >> 6))); }
 
-void launch_bn_stats(const SBnArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bn_stats, bn_grid(a), dim3(256), 0, s, a); }
-void launch_bn_apply(const SBnArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bn_apply, bn_grid(a), dim3(256), 0, s, a); }
+// slices > 1: the sliced instances (nchunk = slices * chunks_per_slice); everything else launches the unsliced ones
+void launch_bn_stats(const SBnArgs& a, hipStream_t s) {
+  if (a.slices > 1) hipLaunchKernelGGL(k_bn_stats<true>, bn_grid(a), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_bn_stats<false>, bn_grid(a), dim3(256), 0, s, a);
+}
+void launch_bn_apply(const SBnArgs& a, hipStream_t s) {
+  if (a.slices > 1) hipLaunchKernelGGL(k_bn_apply<true>, bn_grid(a), dim3(256), 0, s, a);
+  else hipLaunchKernelGGL(k_bn_apply<false>, bn_grid(a), dim3(256), 0, s, a);
+}
 void launch_bn_bwd_stats(const SBnArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bn_bwd_stats, bn_grid(a), dim3(256), 0, s, a); }
 void launch_bn_bwd_dx(const SBnArgs& a, hipStream_t s) {
   if (a.clsp != nullptr) {

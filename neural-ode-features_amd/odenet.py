@@ -122,8 +122,8 @@ class ODEDownsample2(nn.Module):
         self.conv2 = nn.Conv2d(out_ch, out_ch, 4, 2, 1)
         self.apply_conv = False
 
-    # the hand-off `conv2(norm(x))` as one node of the HIP library (downconv.py) where its kernels take the shape; False: the
-    # GroupNorm + ReLU node and nn.Conv2d, as before that node existed (A/B runs, tests)
+    # the hand-off `conv2(norm(x))` as one node of the HIP library (downconv.py: `gn_relu_conv`, or `bn_relu_conv` with norm='batch')
+    # where its kernels take the shape; False: the norm + ReLU and nn.Conv2d, as before those nodes existed (A/B runs, tests)
     fused_handoff = True
 
     def _norm(self, x):
@@ -133,13 +133,35 @@ class ODEDownsample2(nn.Module):
     def _handoff(self, x):
         if not self.fused_handoff:
             return self.conv2(self._norm(x))
-        from .downconv import gn_relu_conv
-        return gn_relu_conv(x, self.norm[0], self.conv2)
+        from . import downconv
+        if isinstance(self.norm[0], nn.BatchNorm2d):      # norm='batch': the node of csrc/bndownconv_api.hip
+            return downconv.bn_relu_conv(x, self.norm[0], self.conv2)
+        return downconv.gn_relu_conv(x, self.norm[0], self.conv2)
+
+    def _batch_trajectory(self, x):
+        """`conv2(norm(slice))` of every slice of a `norm='batch'` trajectory [T, N, C, H, W] on the library's node, or None where it
+        does not take the slices.  BatchNorm's statistics are per slice (model.py:214-216 sends the slices through the norm one by
+        one), so the T slices are not one batch of T N samples: without gradients ONE sliced call normalises every slice with its
+        own statistics (every slice the bits of its own call); with a backward possible, T calls, and autograd sums the shared
+        parameters' gradients."""
+        from . import downconv
+        bn, conv, T = self.norm[0], self.conv2, x.shape[0]
+        flat = x.reshape(-1, *x.shape[2:])
+        if downconv.bn_fusable(flat, bn, conv, T):
+            y = downconv.bn_relu_conv(flat, bn, conv, T)
+            return y.reshape(T, x.shape[1], *y.shape[1:])
+        if all(downconv.bn_fusable(xi, bn, conv) for xi in x):
+            return torch.stack([downconv.bn_relu_conv(xi, bn, conv) for xi in x])
+        return None
 
     def forward(self, x):
         x = self.odeblock(self.conv1(x))
         if x.dim() > 4:
-            if self.apply_conv and self.fused_handoff:
+            if self.apply_conv and self.fused_handoff and isinstance(self.norm[0], nn.BatchNorm2d):
+                y = self._batch_trajectory(x)
+                if y is not None:
+                    return y, y[-1]
+            elif self.apply_conv and self.fused_handoff:
                 from .downconv import fusable, gn_relu_conv
                 flat = x.reshape(-1, *x.shape[2:])
                 if fusable(flat, self.norm[0], self.conv2):
