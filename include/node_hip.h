@@ -886,6 +886,39 @@ int node_ministem_fwd(const node_ministem_shape* shape, const node_ministem_para
 int node_ministem_bwd(const node_ministem_shape* shape, const node_ministem_params* params, const float* x, const float* grad_out,
                       const node_ministem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
 
+/* The `minimal` stem with norm = 'batch' -- model.py:129-145 with model.py:274: the stem above in every respect but the norm,
+ * nn.BatchNorm2d(24, track_running_stats=False) (statistics of the batch in training and evaluation alike) in both places.  The
+ * same shape structure, the same ten tensors in the same order (node_ministem_params / node_ministem_grads, n1_* / n2_* holding
+ * the BatchNorms' weight and bias) and the same shapes taken and refused, with the same messages: in_ch <= 3; filters a power of
+ * two in [64, 4096]; h, w >= 10 (no upper limit on the image); tensors under 2^31 elements.  The convolutions are the stem's
+ * above, used as they are; the norms are BatchNorm + ReLU passes on the [rows = n h w][24] tensors (csrc/kernels_bnministem.hip)
+ * with the conventions of the batch-norm dynamics: statistics in two stages (per chunk of rows the mean and the centred second
+ * moment, combined by Chan's formula in one fixed order), the backward's sums in two stages with fp64 partials, the dx pass in
+ * place on the activation's gradient.
+ *   forward: 7 launches.  node_bnministem_bwd: 12 launches with grads and d_x; grads == NULL (frozen parameters): the
+ *   data-gradient chain alone, 7 launches with d_x; d_x == NULL leaves the transposed first layer out; both NULL: NODE_ERR_NULL.
+ * The backward needs the workspace exactly as the forward left it with keep_for_backward = 1 (one workspace per forward in
+ * flight) and writes (does not accumulate) its results.  The parameter gradients are the same bits with and without d_x, d_x the
+ * same bits with and without grads.  The biases of the first two convolutions stand in front of a BatchNorm, so their gradients
+ * are zero identically: c0_b and c1_b receive the computed column sums of the dx passes, rounding noise around zero.  No
+ * floating-point atomics: every sum runs in a fixed order, so results are bit-reproducible run to run.  The calls never
+ * synchronise, allocate device memory or read back; refused shapes, NULL arguments, parameter or gradient tensors that are not
+ * 16-byte aligned (NODE_ERR_ARG), a workspace that is not 256-byte aligned and a short workspace are rejected before any launch.
+ * The describe call (host only, needs no GPU) fills one node_bnministem_info per norm -- h0 (behind the first convolution), h1
+ * (behind the middle one): every BatchNorm pass runs nchunk workgroups (<= 128; NODE_TUNE_BNMINI_MAXCHUNK sets another cap, for measurements only, and with it
+ * another workspace layout), one per chunk of chunk_rows rows (the last one
+ * last_chunk_rows), each walking its chunk trip_rows rows at a time; wgrad_nsplit / wgrad_rows_per_split of the convolution that
+ * reads the norm's output. */
+typedef struct node_bnministem_info {
+  int32_t rows, chunk_rows, nchunk, last_chunk_rows, trip_rows, wgrad_nsplit, wgrad_rows_per_split;
+} node_bnministem_info;
+size_t node_bnministem_workspace_bytes(const node_ministem_shape* shape, int keep_for_backward);
+int node_bnministem_describe(const node_ministem_shape* shape, node_bnministem_info out[2]);
+int node_bnministem_fwd(const node_ministem_shape* shape, const node_ministem_params* params, const float* x, float* out,
+                        int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
+int node_bnministem_bwd(const node_ministem_shape* shape, const node_ministem_params* params, const float* x, const float* grad_out,
+                        const node_ministem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
 /* Retrieval evaluation -- `evaluate.py retrieval` of the reference (evaluate.py:308-361).  For every query i, with scores
  * s_i[j] = q[i] . x[j] and relevance gt_i[j] = (q_labels[i] == x_labels[j]):
  *   ap[i]   = sklearn average_precision_score(gt_i, s_i): descending scores, equal scores form ONE threshold; a row with no

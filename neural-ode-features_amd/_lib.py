@@ -50,6 +50,7 @@ EXPORTS = [
     'node_downconv_workspace_bytes', 'node_downconv_fwd', 'node_downconv_bwd',
     'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd', 'node_convstem_bwd_dx',
     'node_ministem_workspace_bytes', 'node_ministem_fwd', 'node_ministem_bwd',
+    'node_bnministem_workspace_bytes', 'node_bnministem_describe', 'node_bnministem_fwd', 'node_bnministem_bwd',
     'node_pool_fwd', 'node_pool_bwd',
     'node_bnfunc_workspace_bytes', 'node_bnfunc_fwd', 'node_bnfunc_bwd', 'node_bnfunc_describe',
     'node_bnsolve_workspace_bytes', 'node_bnsolve_fwd', 'node_bnsolve_adjoint',
@@ -255,6 +256,19 @@ class NodeMiniStemShape(C.Structure):
 
 class NodeMiniStemParams(C.Structure):      # node_ministem_params and node_ministem_grads share this layout (and the field names)
     _fields_ = [(k, C.c_void_p) for k in CONVSTEM_PARAM_FIELDS]
+
+
+class NodeBnMiniStemInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('rows', 'chunk_rows', 'nchunk', 'last_chunk_rows', 'trip_rows', 'wgrad_nsplit',
+                                         'wgrad_rows_per_split')]
+
+
+def bnministem_plan(n, in_ch, h, w, filters, eps=1e-5):
+    """The launch plan of the `norm='batch'` minimal stem for an [n, in_ch, h, w] batch: two dicts of node_bnministem_info, one per
+    norm (behind the first convolution, behind the middle one).  Needs no GPU; raises NodeHipError for a shape the node refuses."""
+    info = (NodeBnMiniStemInfo * 2)()
+    check(load().node_bnministem_describe(C.byref(NodeMiniStemShape(n, in_ch, h, w, filters, eps)), info))
+    return [{k: getattr(i, k) for k, _ in i._fields_} for i in info]
 
 
 class NodeConvGeom(C.Structure):
@@ -557,6 +571,14 @@ def load():
     lib.node_ministem_fwd.argtypes = [P(NodeMiniStemShape), P(NodeMiniStemParams), vp, vp, i32, vp, sz, vp]
     lib.node_ministem_bwd.restype = i32
     lib.node_ministem_bwd.argtypes = [P(NodeMiniStemShape), P(NodeMiniStemParams), vp, vp, P(NodeMiniStemParams), vp, vp, sz, vp]
+    lib.node_bnministem_workspace_bytes.restype = sz
+    lib.node_bnministem_workspace_bytes.argtypes = [P(NodeMiniStemShape), i32]
+    lib.node_bnministem_describe.restype = i32
+    lib.node_bnministem_describe.argtypes = [P(NodeMiniStemShape), P(NodeBnMiniStemInfo)]
+    lib.node_bnministem_fwd.restype = i32
+    lib.node_bnministem_fwd.argtypes = [P(NodeMiniStemShape), P(NodeMiniStemParams), vp, vp, i32, vp, sz, vp]
+    lib.node_bnministem_bwd.restype = i32
+    lib.node_bnministem_bwd.argtypes = [P(NodeMiniStemShape), P(NodeMiniStemParams), vp, vp, P(NodeMiniStemParams), vp, vp, sz, vp]
     lib.node_pool_fwd.restype = i32
     lib.node_pool_fwd.argtypes = [P(NodePoolShape), vp, vp, vp, vp, vp]
     lib.node_pool_bwd.restype = i32

@@ -10,6 +10,7 @@ and shapes the kernels refuse run the module sequence -- on a HIP device with th
 A `norm='batch'` stem (both norms `nn.BatchNorm2d(64, track_running_stats=False)`, model.py:274) is one node too:
 `_BnConvStemFn` (`node_bnconvstem_fwd / _bwd / _bwd_dx`, csrc/bnconvstem_api.hip), the same launch plan around the BatchNorm
 passes of the batch-norm dynamics; filters may be any multiple of 64.  `ConvStem.fused_batch = False` runs its module sequence.
+(The 24-channel `minimal` stem with `norm='batch'` has a node of its own in ministem.py, `_BnMiniStemFn`.)
 """
 from __future__ import annotations
 
