@@ -745,7 +745,7 @@ __global__ __launch_bounds__(256) void k_stem_gn_fwd(const SGnArgs a) {
   float s2 = 0.f;
   for (int px = pg; px < HW; px += PG) {
     const float d = tile[px * CB + c] - mean;
-    s2 += d * d;
+    s2 = __builtin_fmaf(d, d, s2);      // (what `s2 += d * d` compiled to here; written out because k_stem_gn_fwd_fl must round the same way)
   }
   group_sums(s2, red, grstd, CB, a.cpg, t);
   const int ngrp = CB / a.cpg;
@@ -862,6 +862,283 @@ __global__ __launch_bounds__(256) void k_stem_gn_bwd(const SGnArgs a) {
     const size_t o = ((size_t)n * HW + px) * C + c0 + 8 * q;
     if constexpr (SKIP) {
       const float4 k0 = *reinterpret_cast<const float4*>(a.skip + o), k1 = *reinterpret_cast<const float4*>(a.skip + o + 4);
+      v[0] += k0.x; v[1] += k0.y; v[2] += k0.z; v[3] += k0.w;
+      v[4] += k1.x; v[5] += k1.y; v[6] += k1.z; v[7] += k1.w;
+    }
+    const float4 p0 = make_float4(v[0], v[1], v[2], v[3]), p1 = make_float4(v[4], v[5], v[6], v[7]);
+    if (a.dh) {
+      *reinterpret_cast<float4*>(a.dh + o) = p0;
+      *reinterpret_cast<float4*>(a.dh + o + 4) = p1;
+    }
+    if (a.dh3) {
+      u32x4 hh, mm, ll;
+      split8(p0, p1, hh, mm, ll);
+      *reinterpret_cast<u32x4*>(a.dh3 + o) = hh;
+      *reinterpret_cast<u32x4*>(a.dh3 + o + a.dh_plane) = mm;
+      *reinterpret_cast<u32x4*>(a.dh3 + o + 2 * a.dh_plane) = ll;
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------
+// The same two passes with their requests kept in flight (the default; NODE_TUNE_STEM_GN=0 launches the kernels above).
+// Every sum is the chain of additions it is above, so the results are the same bits:
+//   * block, grid and the thread -> (channel, pixels pg, pg + PG, ...) assignment of the statistics are the ones above; which
+//     (sample, block) a workgroup takes is not (gn_block_id);
+//   * the fill issues GN_NB independent 16-byte loads per thread before the first LDS write (the last, partial batch re-reads
+//     the block's last request instead of branching around loads, and drops the copies into `dump`: 16 bytes of the sums'
+//     scratch, which nothing reads before the barrier behind the fill);
+//   * the serial sums read their LDS operands eight at a time ahead of the additions, which stay in order;
+//   * the store loop holds its eight channels' gamma / beta / statistics in registers (a thread's channels never change:
+//     256 % (CB / 8) == 0).
+// CB and cpg are powers of two here (stem_gn_cb refuses every other shape).
+// Measured and not kept (profiles/stem_gn_ab.txt): narrower channel blocks under the same summation stride, i.e. more and smaller
+// workgroups per CU.  With a sample's blocks in one L2 (gn_block_id) blocks half as wide took 1.3 us off each 15 x 15 backward
+// (15.4 -> 14.1) and nothing off the other four launches; 8-channel blocks made the 30 x 30 launches 20 - 25 % slower.
+// ----------------------------------------------------------------------------
+constexpr int GN_NB = 8;
+__device__ __forceinline__ int gn_log2(int v) { return 31 - __clz(v); }
+// Workgroups b and b + 8 share an XCD and its L2.  A block of 16 channels is 64 bytes of every 128-byte line of its sample's rows
+// (32 of the triples' lines): dealt out in launch order, the C / CB blocks of a sample sit on different XCDs, each line is fetched
+// by several L2s and leaves them in pieces.  This id gives every XCD a contiguous run of (sample, block) pairs instead, so a
+// sample's blocks meet in one L2.  A bijection for every grid size; which block a workgroup takes changes no result: on a part
+// or partition mode that deals workgroups out differently (another XCD count, no round-robin) only the locality is lost.
+__device__ __forceinline__ int gn_block_id() {
+  const int b = blockIdx.x, q = gridDim.x >> 3, r = gridDim.x & 7, x = b & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
+}
+
+template <int NS>
+__device__ __forceinline__ void gn_fill(float* tile0, const float* __restrict__ src0, float* tile1, const float* __restrict__ src1,
+                                        float* dump, int C, int lq4, int total, int t) {
+  const int qm = (1 << lq4) - 1;
+  int idx = t;
+  for (; idx + (GN_NB - 1) * 256 < total; idx += GN_NB * 256) {
+    float4 r0[GN_NB], r1[GN_NB];
+#pragma unroll
+    for (int u = 0; u < GN_NB; ++u) {
+      const int i = idx + 256 * u;
+      const size_t o = (size_t)(i >> lq4) * C + 4 * (i & qm);
+      r0[u] = *reinterpret_cast<const float4*>(src0 + o);
+      if constexpr (NS == 2) r1[u] = *reinterpret_cast<const float4*>(src1 + o);
+    }
+#pragma unroll
+    for (int u = 0; u < GN_NB; ++u) {
+      *reinterpret_cast<float4*>(tile0 + 4 * (idx + 256 * u)) = r0[u];      // (pixel * CB + 4 q = 4 i)
+      if constexpr (NS == 2) *reinterpret_cast<float4*>(tile1 + 4 * (idx + 256 * u)) = r1[u];
+    }
+  }
+  if (idx < total) {
+    float4 r0[GN_NB], r1[GN_NB];
+#pragma unroll
+    for (int u = 0; u < GN_NB; ++u) {
+      const int i = min(idx + 256 * u, total - 1);
+      const size_t o = (size_t)(i >> lq4) * C + 4 * (i & qm);
+      r0[u] = *reinterpret_cast<const float4*>(src0 + o);
+      if constexpr (NS == 2) r1[u] = *reinterpret_cast<const float4*>(src1 + o);
+    }
+#pragma unroll
+    for (int u = 0; u < GN_NB; ++u) {       // (an `if` around the write would take its load along: one request per branch)
+      const bool real = idx + 256 * u < total;
+      *reinterpret_cast<float4*>(real ? tile0 + 4 * (idx + 256 * u) : dump) = r0[u];
+      if constexpr (NS == 2) *reinterpret_cast<float4*>(real ? tile1 + 4 * (idx + 256 * u) : dump) = r1[u];
+    }
+  }
+}
+
+// group_sums with the operands of each chain read eight ahead: grp[g] = ((red[g cpg] + red[g cpg + 1]) + ... ) over
+// (j, k), j < PG outer, k < cpg inner -- the order above
+__device__ __forceinline__ void group_sums_ahead(float v, float* red, float* grp, int CB, int lcpg, int PG, int t) {
+  red[t] = v;
+  __syncthreads();
+  if (t < (CB >> lcpg)) {
+    const float* r0 = red + (t << lcpg);
+    const int n = PG << lcpg, km = (1 << lcpg) - 1;
+    float s = 0.f;
+    for (int i = 0; i < n; i += 8) {
+      float x[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int ii = min(i + u, n - 1);
+        x[u] = r0[(ii >> lcpg) * CB + (ii & km)];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (i + u < n) s += x[u];
+    }
+    grp[t] = s;
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_stem_gn_fwd_fl(const SGnArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int t = threadIdx.x;
+  const int CB = a.CB, HW = a.HW, C = a.C;
+  float* tile = reinterpret_cast<float*>(smem);
+  float* red = tile + (size_t)HW * CB;      // [256]
+  float* gmean = red + 256;                 // [128]
+  float* grstd = gmean + 128;               // [128]
+  const int nblk = C / CB, bid = gn_block_id();
+  const int n = bid / nblk, c0 = (bid - n * nblk) * CB;
+  const int lcb = gn_log2(CB), lcpg = gn_log2(a.cpg);
+  gn_fill<1>(tile, a.h + ((size_t)n * HW) * C + c0, nullptr, nullptr, red, C, lcb - 2, HW << (lcb - 2), t);
+  __syncthreads();
+  const int c = t & (CB - 1), pg = t >> lcb, PG = 256 >> lcb;
+  const float inv_m = 1.f / (float)(a.cpg * HW);
+  float s = 0.f;
+#pragma unroll 4
+  for (int px = pg; px < HW; px += PG) s += tile[px * CB + c];
+  group_sums_ahead(s, red, gmean, CB, lcpg, PG, t);
+  const float mean = gmean[c >> lcpg] * inv_m;
+  float s2 = 0.f;
+#pragma unroll 4
+  for (int px = pg; px < HW; px += PG) {
+    const float d = tile[px * CB + c] - mean;
+    s2 = __builtin_fmaf(d, d, s2);      // (as above; left to contraction, the unrolled loop multiplies in pairs and adds: two roundings)
+  }
+  group_sums_ahead(s2, red, grstd, CB, lcpg, PG, t);
+  const int ngrp = CB >> lcpg;
+  if (t < ngrp) {
+    const float m = gmean[t] * inv_m, rs = rsqrtf(grstd[t] * inv_m + a.eps);
+    float* st = a.stats + ((size_t)n * (C >> lcpg) + (c0 >> lcpg) + t) * 2;
+    st[0] = m;
+    st[1] = rs;
+  }
+  __syncthreads();
+  if (t < ngrp) {
+    const float m = gmean[t] * inv_m, rs = rsqrtf(grstd[t] * inv_m + a.eps);
+    gmean[t] = m;
+    grstd[t] = rs;
+  }
+  __syncthreads();
+  const int lq8 = lcb - 3, q = t & ((1 << lq8) - 1), pstep = 256 >> lq8;
+  float gm[8], gr[8], ga[8], be[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int cc = 8 * q + k, g = cc >> lcpg;
+    gm[k] = gmean[g];
+    gr[k] = grstd[g];
+    ga[k] = a.gamma[c0 + cc];
+    be[k] = a.beta[c0 + cc];
+  }
+#pragma unroll 2
+  for (int px = t >> lq8; px < HW; px += pstep) {
+    const float4 p0 = *reinterpret_cast<const float4*>(tile + px * CB + 8 * q);
+    const float4 p1 = *reinterpret_cast<const float4*>(tile + px * CB + 8 * q + 4);
+    float v[8] = {p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float y = (v[k] - gm[k]) * gr[k] * ga[k] + be[k];
+      v[k] = fmaxf(y, 0.f);
+    }
+    u32x4 hh, mm, ll;
+    split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), hh, mm, ll);
+    bf16_t* dst = a.a3 + ((size_t)n * HW + px) * C + c0 + 8 * q;
+    *reinterpret_cast<u32x4*>(dst) = hh;
+    *reinterpret_cast<u32x4*>(dst + a.a_plane) = mm;
+    *reinterpret_cast<u32x4*>(dst + 2 * a.a_plane) = ll;
+  }
+}
+
+template <bool SKIP>
+__global__ __launch_bounds__(256) void k_stem_gn_bwd_fl(const SGnArgs a) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const int CB = a.CB, HW = a.HW, C = a.C;
+  float* txh = reinterpret_cast<float*>(smem);          // h, then xhat
+  float* tdy = txh + (size_t)HW * CB;                     // da, then dy
+  float* redA = tdy + (size_t)HW * CB;                    // [256]
+  float* redB = redA + 256;                               // [256]
+  float* gmean = redB + 256;                              // [128] each
+  float* grstd = gmean + 128;
+  float* gs1 = grstd + 128;
+  float* gs2 = gs1 + 128;
+  const int t = threadIdx.x;
+  const int nblk = C / CB, bid = gn_block_id();
+  const int n = bid / nblk, c0 = (bid - n * nblk) * CB;
+  const int lcb = gn_log2(CB), lcpg = gn_log2(a.cpg);
+  gn_fill<2>(txh, a.h + ((size_t)n * HW) * C + c0, tdy, a.da + ((size_t)n * HW) * C + c0, redA, C, lcb - 2, HW << (lcb - 2), t);
+  const int ngrp = CB >> lcpg;
+  if (t < ngrp) {
+    const float* st = a.stats + ((size_t)n * (C >> lcpg) + (c0 >> lcpg) + t) * 2;
+    gmean[t] = st[0];
+    grstd[t] = st[1];
+  }
+  __syncthreads();
+  const int c = t & (CB - 1), pg = t >> lcb, PG = 256 >> lcb;
+  const float mean = gmean[c >> lcpg], rstd = grstd[c >> lcpg], gam = a.gamma[c0 + c], bet = a.beta[c0 + c];
+  float sA = 0.f, sB = 0.f;
+#pragma unroll 4
+  for (int px = pg; px < HW; px += PG) {
+    const float xh = (txh[px * CB + c] - mean) * rstd;
+    const float y = xh * gam + bet;
+    const float dy = y > 0.f ? tdy[px * CB + c] : 0.f;
+    txh[px * CB + c] = xh;
+    tdy[px * CB + c] = dy;
+    sA += dy;
+    sB += dy * xh;
+  }
+  redA[t] = sA;
+  redB[t] = sB;
+  __syncthreads();
+  if (t < CB) {
+    float A = 0.f, B = 0.f;
+    for (int j0 = 0; j0 < PG; j0 += 8) {
+      float xa[8], xb[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int j = min(j0 + u, PG - 1);
+        xa[u] = redA[j * CB + t];
+        xb[u] = redB[j * CB + t];
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (j0 + u < PG) { A += xa[u]; B += xb[u]; }
+    }
+    a.gpart[((size_t)n * 2 + 0) * C + c0 + t] = B;      // dgamma
+    a.gpart[((size_t)n * 2 + 1) * C + c0 + t] = A;      // dbeta
+    redA[t] = A * gam;      // (t < CB: c == t)
+    redB[t] = B * gam;
+  }
+  __syncthreads();
+  if (t < ngrp) {
+    float s1 = 0.f, s2 = 0.f;
+    for (int k = 0; k < a.cpg; ++k) { s1 += redA[t * a.cpg + k]; s2 += redB[t * a.cpg + k]; }
+    gs1[t] = s1;
+    gs2[t] = s2;
+  }
+  __syncthreads();
+  const float inv_m = 1.f / (float)(a.cpg * HW);
+  const int lq8 = lcb - 3, q = t & ((1 << lq8) - 1), pstep = 256 >> lq8;
+  float gr[8], ga[8], g1[8], g2[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int cc = 8 * q + k, g = cc >> lcpg;
+    gr[k] = grstd[g];
+    ga[k] = a.gamma[c0 + cc];
+    g1[k] = gs1[g];
+    g2[k] = gs2[g];
+  }
+  // (SKIP: one pixel per trip -- over two, the compiler waited for each of the four `skip` loads on its own)
+  constexpr int PX_PER_TRIP = SKIP ? 1 : 2;
+#pragma unroll PX_PER_TRIP
+  for (int px = t >> lq8; px < HW; px += pstep) {
+    const size_t o = ((size_t)n * HW + px) * C + c0 + 8 * q;
+    float4 k0, k1;
+    if constexpr (SKIP) {
+      k0 = *reinterpret_cast<const float4*>(a.skip + o);
+      k1 = *reinterpret_cast<const float4*>(a.skip + o + 4);
+    }
+    const float4 x0 = *reinterpret_cast<const float4*>(txh + px * CB + 8 * q), x1 = *reinterpret_cast<const float4*>(txh + px * CB + 8 * q + 4);
+    const float4 d0 = *reinterpret_cast<const float4*>(tdy + px * CB + 8 * q), d1 = *reinterpret_cast<const float4*>(tdy + px * CB + 8 * q + 4);
+    const float xs[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w}, ds[8] = {d0.x, d0.y, d0.z, d0.w, d1.x, d1.y, d1.z, d1.w};
+    float v[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const float xh = xs[k], dy = ds[k];
+      v[k] = gr[k] * (dy * ga[k] - (g1[k] + xh * g2[k]) * inv_m);
+    }
+    if constexpr (SKIP) {
       v[0] += k0.x; v[1] += k0.y; v[2] += k0.z; v[3] += k0.w;
       v[4] += k1.x; v[5] += k1.y; v[6] += k1.z; v[7] += k1.w;
     }
@@ -1166,7 +1443,16 @@ int stem_gn_cb(int HW, int C, int cpg) {
   if (C % cb != 0 || cb % cpg != 0) return 0;
   return cb;
 }
+// NODE_TUNE_STEM_GN=0 (read per call): the GroupNorm passes as k_stem_gn_fwd / k_stem_gn_bwd (A/B runs, tests).  Default:
+// k_stem_gn_*_fl -- same block, same grid, same LDS, the same bits.
+static bool stem_gn_fl() { return env_int("NODE_TUNE_STEM_GN", 1) != 0; }
 void launch_stem_gn_fwd(const SGnArgs& a, hipStream_t s) {
+  if (stem_gn_fl()) {
+    static bool attr[MAX_DEVICES] = {};
+    allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_fwd_fl), attr);
+    hipLaunchKernelGGL(k_stem_gn_fwd_fl, dim3(a.N * (a.C / a.CB)), dim3(256), ((size_t)a.HW * a.CB + 512) * sizeof(float), s, a);
+    return;
+  }
   static bool attr[MAX_DEVICES] = {};
   allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_fwd), attr);
   hipLaunchKernelGGL(k_stem_gn_fwd, dim3(a.N * (a.C / a.CB)), dim3(256), ((size_t)a.HW * a.CB + 512) * sizeof(float), s, a);
@@ -1174,6 +1460,18 @@ void launch_stem_gn_fwd(const SGnArgs& a, hipStream_t s) {
 void launch_stem_gn_bwd(const SGnArgs& a, hipStream_t s) {
   const dim3 grid(a.N * (a.C / a.CB));
   const size_t lds = ((size_t)2 * a.HW * a.CB + 1024) * sizeof(float);
+  if (stem_gn_fl()) {
+    if (a.skip) {
+      static bool attr[MAX_DEVICES] = {};
+      allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_bwd_fl<true>), attr);
+      hipLaunchKernelGGL(k_stem_gn_bwd_fl<true>, grid, dim3(256), lds, s, a);
+    } else {
+      static bool attr[MAX_DEVICES] = {};
+      allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_bwd_fl<false>), attr);
+      hipLaunchKernelGGL(k_stem_gn_bwd_fl<false>, grid, dim3(256), lds, s, a);
+    }
+    return;
+  }
   if (a.skip) {
     static bool attr[MAX_DEVICES] = {};
     allow_full_lds(reinterpret_cast<const void*>(k_stem_gn_bwd<true>), attr);
