@@ -402,6 +402,24 @@ size_t node_head_loss_scratch_bytes(int n);
 int node_head_loss_fwd(const node_head_loss* head, void* stream);
 int node_head_loss_bwd(const node_head_loss* head, const node_head_loss_grad* grads, void* stream);
 
+/* node_head_loss_fwd for `slices` trajectories' slices in ONE launch: rows [s*n, (s+1)*n) are slice s, `target` [n] is shared.
+ * logits [slices*n, classes] (computed from pooled [slices*n, c], or given with pooled == NULL); loss [slices] (NODE_REDUCE_SUM
+ * only); stat [slices, 2] = {loss, hits}.  Every logit, loss[s] and stat[s] the bits of node_head_loss_fwd on slice s alone.
+ * `scratch`: node_head_loss_slices_scratch_bytes(slices, n) bytes, ZERO before its first use, not shared between streams and
+ * kept for ONE value of `slices` (the arrival counters, one per slice, lie in front of the partials; any n up to the one it
+ * was sized for); needed when target != NULL; loss and stat are optional then, but one of them must be given; slices <= 65535. */
+typedef struct node_head_loss_slices { int32_t slices, n, c, classes; const float *pooled, *weight, *bias; const int64_t* target;
+                                       float *logits, *loss, *stat, *scratch; } node_head_loss_slices;
+size_t node_head_loss_slices_scratch_bytes(int slices, int n);
+int node_head_loss_slices_fwd(const node_head_loss_slices* head, void* stream);
+
+/* u = relu(GroupNorm(z)) per sample for two trajectories a, b [rows, c, h, w] (rows = T*N), never written:
+ * out [rows, 2] = { sqrt(sum (ub - ua)^2), cosine similarity of ua and ub as F.cosine_similarity defines it (eps 1e-8) }
+ * -- diff.py:111-123's two numbers per (time slice, sample).  ONE launch, each trajectory read once, fixed summation order,
+ * no atomics.  Shapes: those of node_head_fwd (shape->n = rows). */
+int node_gn_relu_distance(const node_shape* shape /* n = rows */, const float* a, const float* b, const float* gamma,
+                          const float* beta, float* out, void* stream);
+
 /* The optimizer step of the training loop -- train.py:136 (`torch.optim.SGD(params, lr, momentum=0.9, weight_decay=wd)`)
  * stepped at train.py:56-58 -- for ALL parameter tensors of the model in one launch (per 64 tensors):
  *   g = grad_scale * grad + weight_decay * p;  buf = momentum * buf + g;  p -= lr * buf
@@ -672,6 +690,14 @@ int node_bnhead_fwd(const node_bnfunc_shape* shape, const float* z, const float*
                     float* pooled, float* stats, void* scratch, void* stream);
 int node_bnhead_bwd(const node_bnfunc_shape* shape, const float* z, const float* gamma, const float* beta, const float* scale,
                     const float* stats, const float* g_pooled, float* dz, float* dgamma, float* dbeta, void* scratch, void* stream);
+
+/* node_bnhead_fwd with the statistics PER SLICE (the reference normalises slice by slice): z [slices, n, c, h, w],
+ * pooled [slices, n, c], stats [slices, 2, c]; two launches; every slice the bits of node_bnhead_fwd on it alone.  Forward only
+ * (no dropout scale).  Shapes: those of node_bnhead_fwd for a slice, 1 <= slices <= 65535; scratch: 8-byte aligned,
+ * node_bnhead_slices_scratch_bytes bytes (0 for a shape the entry refuses). */
+size_t node_bnhead_slices_scratch_bytes(const node_bnfunc_shape* shape, int slices);
+int node_bnhead_fwd_slices(const node_bnfunc_shape* shape, int slices, const float* z, const float* gamma, const float* beta,
+                           float* pooled, float* stats, void* scratch, void* stream);
 
 /* A whole SOLVE of these dynamics, forward and continuous adjoint: what the generic solver does around node_bnfunc_fwd / _bwd
  * (stage states, Hairer's initial step, error norms, accept / reject, dense output, FSAL: the node_flat_* kernels), driven from

@@ -19,7 +19,7 @@ from .downconv import bn_relu_conv, gn_relu_conv  # noqa: F401
 from .pool import max_pool_4s2, trajectory_pool  # noqa: F401
 from .resnet import ResNet, ResidualTrunk, build_model  # noqa: F401
 from .optim import FusedAdam, FusedSGD  # noqa: F401
-from .head import cross_entropy, linear, linear_cross_entropy  # noqa: F401
+from .head import cross_entropy, linear, linear_cross_entropy, trajectory_distance, trajectory_loss  # noqa: F401
 
 __all__ = ['odeint', 'odeint_adjoint', 'ODEBlock', 'ODEfunc', 'ConcatConv2d', 'ODENet', 'StackedODENet', 'ResNet', 'ResidualTrunk',
            'ODEDownsample', 'ODEDownsample2', 'ConvStem', 'MinimalStem', 'max_pool_4s2', 'trajectory_pool', 'dp']

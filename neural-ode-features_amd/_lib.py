@@ -59,6 +59,8 @@ EXPORTS = [
     'node_bnstem_workspace_bytes', 'node_bnstem_describe', 'node_bnstem_fwd', 'node_bnstem_bwd',
     'node_bnconvstem_workspace_bytes', 'node_bnconvstem_describe', 'node_bnconvstem_fwd', 'node_bnconvstem_bwd', 'node_bnconvstem_bwd_dx',
     'node_bndownconv_workspace_bytes', 'node_bndownconv_describe', 'node_bndownconv_fwd', 'node_bndownconv_bwd',
+    'node_head_loss_slices_scratch_bytes', 'node_head_loss_slices_fwd', 'node_bnhead_slices_scratch_bytes', 'node_bnhead_fwd_slices',
+    'node_gn_relu_distance',
 ]
 
 
@@ -284,6 +286,12 @@ class NodeHeadLoss(C.Structure):
                 ('logits', C.c_void_p), ('loss', C.c_void_p), ('stat', C.c_void_p), ('scratch', C.c_void_p)]
 
 
+class NodeHeadLossSlices(C.Structure):
+    _fields_ = [('slices', C.c_int32), ('n', C.c_int32), ('c', C.c_int32), ('classes', C.c_int32),
+                ('pooled', C.c_void_p), ('weight', C.c_void_p), ('bias', C.c_void_p), ('target', C.c_void_p),
+                ('logits', C.c_void_p), ('loss', C.c_void_p), ('stat', C.c_void_p), ('scratch', C.c_void_p)]
+
+
 class NodeHeadLossGrad(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ('grad_loss', 'grad_logits', 'd_logits', 'd_pooled', 'd_weight', 'd_bias')]
 
@@ -451,6 +459,12 @@ def load():
     lib.node_head_loss_fwd.argtypes = [P(NodeHeadLoss), vp]
     lib.node_head_loss_bwd.restype = i32
     lib.node_head_loss_bwd.argtypes = [P(NodeHeadLoss), P(NodeHeadLossGrad), vp]
+    lib.node_head_loss_slices_scratch_bytes.restype = sz
+    lib.node_head_loss_slices_scratch_bytes.argtypes = [i32, i32]
+    lib.node_head_loss_slices_fwd.restype = i32
+    lib.node_head_loss_slices_fwd.argtypes = [P(NodeHeadLossSlices), vp]
+    lib.node_gn_relu_distance.restype = i32
+    lib.node_gn_relu_distance.argtypes = [P(NodeShape), vp, vp, vp, vp, vp, vp]
     lib.node_flat_workspace_bytes.restype = sz
     lib.node_flat_workspace_bytes.argtypes = [i32]
     lib.node_flat_begin.restype = i32
@@ -533,6 +547,10 @@ def load():
     lib.node_bnhead_fwd.argtypes = [P(NodeBnfuncShape), vp, vp, vp, vp, vp, vp, vp, vp]
     lib.node_bnhead_bwd.restype = i32
     lib.node_bnhead_bwd.argtypes = [P(NodeBnfuncShape), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.node_bnhead_slices_scratch_bytes.restype = sz
+    lib.node_bnhead_slices_scratch_bytes.argtypes = [P(NodeBnfuncShape), i32]
+    lib.node_bnhead_fwd_slices.restype = i32
+    lib.node_bnhead_fwd_slices.argtypes = [P(NodeBnfuncShape), i32, vp, vp, vp, vp, vp, vp, vp]
     lib.node_downconv_workspace_bytes.restype = sz
     lib.node_downconv_workspace_bytes.argtypes = [P(NodeDownConvShape), i32]
     lib.node_downconv_fwd.restype = i32

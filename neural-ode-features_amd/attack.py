@@ -365,9 +365,23 @@ def attack(args):
     return path
 
 
+def _diff_fused(extractor, x):
+    """`diff`'s two numbers per time point from `head.trajectory_distance`'s kernel: a HIP fp32 batch through an extractor whose
+    stem is no ODE stem (those return a tuple) and whose head, after `to_features_extractor(keep_pool=False)`, is an affine
+    GroupNorm + ReLU without hooks.  `FCClassifier.fused_trajectory = False`: the chain of tensor operations, as before."""
+    from .odenet import FCClassifier, ODEDownsample, ODEDownsample2
+    head = extractor.classifier
+    return (FCClassifier.fused_trajectory and x.is_cuda and x.dtype == torch.float32
+            and not isinstance(extractor.downsample, (ODEDownsample, ODEDownsample2))
+            and isinstance(head, torch.nn.Sequential) and len(head) == 2 and isinstance(head[0], torch.nn.GroupNorm)
+            and head[0].affine and isinstance(head[1], torch.nn.ReLU)
+            and not any(m._forward_hooks or m._forward_pre_hooks for m in (extractor, head, head[0], head[1])))
+
+
 def diff(args):
     """diff.py:18-127."""
     import numpy as np
+    from .head import trajectory_distance
     model, p, xte, yte, pre = _load(args)
     if getattr(p, 'model', 'odenet') == 'resnet':
         raise SystemExit('attack diff compares trajectories of the ODE block: the run is a ResNet')
@@ -397,13 +411,19 @@ def diff(args):
         ok = (r.found_iteration > 0).cpu()
         with torch.no_grad():
             a, b = ((v - mean) / std if mean is not None else v for v in (x, r.adversarial))
-            traj0 = extractor(a)       # [T, n, C, H, W]
-            traj1 = extractor(b)
-        T = traj0.shape[0]
-        traj0 = traj0.reshape(T, len(ids), -1).transpose(0, 1)
-        traj1 = traj1.reshape(T, len(ids), -1).transpose(0, 1)
-        l2 = (traj1 - traj0).pow(2).sum(-1).sqrt().cpu()
-        cos = F.cosine_similarity(traj1, traj0, dim=-1).cpu()
+            if _diff_fused(extractor, a):
+                # the RAW trajectories into one launch that normalises both in registers and writes neither (head.trajectory_distance)
+                l2, cos = trajectory_distance(extractor.odeblock(extractor.downsample(a)),
+                                              extractor.odeblock(extractor.downsample(b)), extractor.classifier[0])
+                l2, cos = l2.t().cpu(), cos.t().cpu()
+            else:
+                traj0 = extractor(a)       # [T, n, C, H, W]
+                traj1 = extractor(b)
+                T = traj0.shape[0]
+                traj0 = traj0.reshape(T, len(ids), -1).transpose(0, 1)
+                traj1 = traj1.reshape(T, len(ids), -1).transpose(0, 1)
+                l2 = (traj1 - traj0).pow(2).sum(-1).sqrt().cpu()
+                cos = F.cosine_similarity(traj1, traj0, dim=-1).cpu()
         rows_l2, rows_cos = [], []
         for j, s in enumerate(ids):
             if not bool(ok[j]):

@@ -183,6 +183,19 @@ int node_head_fwd(const node_shape* shape, const float* z, const float* gamma, c
   return NODE_OK;
 }
 
+int node_gn_relu_distance(const node_shape* shape, const float* a, const float* b, const float* gamma, const float* beta, float* out,
+                          void* stream) {
+  char why[200];
+  const int rc = head_check(shape, why, sizeof(why));
+  if (rc != NODE_OK) return fail(rc, "%s", why);
+  if (!a || !b || !gamma || !beta || !out) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  if ((((uintptr_t)a) | ((uintptr_t)b)) & 15) return fail(NODE_ERR_ARG, "a and b must be 16-byte aligned");
+  launch_gn_relu_distance(*shape, a, b, gamma, beta, out, (hipStream_t)stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of node_gn_relu_distance failed: %s", hipGetErrorString(e));
+  return NODE_OK;
+}
+
 int node_head_bwd(const node_shape* shape, const float* z, const float* gamma, const float* beta, const float* scale,
                   const float* stats, const float* g_pooled, float* dz, float* gpart, float* gsum, void* stream) {
   char why[200];

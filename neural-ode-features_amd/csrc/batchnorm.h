@@ -117,6 +117,9 @@ struct SBnHeadArgs {
 int bnhead_chunk_samples(int N, int C);      // samples per chunk: <= BNHEAD_MAX_CHUNKS chunks, about 2048 workgroups at most
 void launch_bnhead_stats(const SBnHeadArgs& a, hipStream_t s);
 void launch_bnhead_apply(const SBnHeadArgs& a, hipStream_t s);
+// the two forward passes for `slices` tensors [N][C][HW] behind one another, statistics per slice (a.scale unused: forward only)
+void launch_bnhead_stats_slices(const SBnHeadArgs& a, int slices, hipStream_t s);
+void launch_bnhead_apply_slices(const SBnHeadArgs& a, int slices, hipStream_t s);
 void launch_bnhead_bwd_stats(const SBnHeadArgs& a, hipStream_t s);
 void launch_bnhead_bwd_dx(const SBnHeadArgs& a, hipStream_t s);
 

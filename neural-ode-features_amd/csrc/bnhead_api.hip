@@ -66,6 +66,34 @@ int node_bnhead_fwd(const node_bnfunc_shape* shape, const float* z, const float*
   return launch_ok("bnhead_apply");
 }
 
+size_t node_bnhead_slices_scratch_bytes(const node_bnfunc_shape* shape, int slices) {
+  if (check_head_shape(shape) != NODE_OK) return 0;
+  if (slices <= 0 || slices > 65535) { fail(NODE_ERR_UNSUPPORTED, "the sliced batch-norm head takes 1 to 65535 slices (got %d)", slices); return 0; }
+  return (size_t)slices * node_bnhead_scratch_bytes(shape);
+}
+
+int node_bnhead_fwd_slices(const node_bnfunc_shape* shape, int slices, const float* z, const float* gamma, const float* beta,
+                           float* pooled, float* stats, void* scratch, void* stream) {
+  int rc = check_head_shape(shape);
+  if (rc != NODE_OK) return rc;
+  if (slices <= 0 || slices > 65535) return fail(NODE_ERR_UNSUPPORTED, "the sliced batch-norm head takes 1 to 65535 slices (got %d)", slices);
+  if ((rc = check_f32(z, "z", true)) != NODE_OK || (rc = check_f32(gamma, "gamma", true)) != NODE_OK ||
+      (rc = check_f32(beta, "beta", true)) != NODE_OK || (rc = check_f32(pooled, "pooled", true)) != NODE_OK ||
+      (rc = check_f32(stats, "stats", true)) != NODE_OK)
+    return rc;
+  if (!scratch) return fail(NODE_ERR_NULL, "scratch is NULL");
+  if (((uintptr_t)scratch) & 7) return fail(NODE_ERR_ARG, "scratch must be 8-byte aligned");
+  // (the shape is a SLICE's: head_args picks the chunking node_bnhead_fwd picks for it; a slice's partials take the
+  //  nchunk * 2 * C floats at the head of its node_bnhead_scratch_bytes share)
+  SBnHeadArgs a = head_args(shape, z, gamma, beta, nullptr, stats);
+  a.pooled = pooled; a.part = static_cast<float*>(scratch);
+  hipStream_t st = (hipStream_t)stream;
+  launch_bnhead_stats_slices(a, slices, st);
+  if ((rc = launch_ok("bnhead_stats_slices")) != NODE_OK) return rc;
+  launch_bnhead_apply_slices(a, slices, st);
+  return launch_ok("bnhead_apply_slices");
+}
+
 int node_bnhead_bwd(const node_bnfunc_shape* shape, const float* z, const float* gamma, const float* beta, const float* scale,
                     const float* stats, const float* g_pooled, float* dz, float* dgamma, float* dbeta, void* scratch, void* stream) {
   int rc = check_head_shape(shape);

@@ -65,7 +65,7 @@ __device__ __forceinline__ const float* plane_of(const SBnHeadArgs& a, int n, in
 // ============================================================================
 // forward, stage 1: per (chunk, channel) the chunk's mean and centred second moment
 // ============================================================================
-__global__ __launch_bounds__(256) void k_bnhead_stats(const SBnHeadArgs a) {
+__device__ __forceinline__ void bnhead_stats_body(const SBnHeadArgs& a) {
   __shared__ float sm[4];
   const HGeo g = head_geo(a);
   float s = 0.f;
@@ -88,6 +88,7 @@ __global__ __launch_bounds__(256) void k_bnhead_stats(const SBnHeadArgs a) {
     a.part[((size_t)g.chunk * 2 + 1) * a.C + g.c] = m2;
   }
 }
+__global__ __launch_bounds__(256) void k_bnhead_stats(const SBnHeadArgs a) { bnhead_stats_body(a); }
 
 // The batch statistics of channel c from its partials: lane k < nchunk holds chunk k, six xor steps merge neighbours by Chan's formula,
 // always (lower lanes' set, higher lanes' set) in that order, so every lane of every wave of every workgroup ends with the same bits.
@@ -118,7 +119,7 @@ __device__ __forceinline__ void head_combine(const SBnHeadArgs& a, int c, int la
 // ============================================================================
 // forward, stage 2: pooled = scale * mean_px relu(xhat gamma + beta)
 // ============================================================================
-__global__ __launch_bounds__(256) void k_bnhead_apply(const SBnHeadArgs a) {
+__device__ __forceinline__ void bnhead_apply_body(const SBnHeadArgs& a) {
   const HGeo g = head_geo(a);
   float mean, rstd;
   head_combine(a, g.c, g.lane, mean, rstd);
@@ -142,6 +143,22 @@ __global__ __launch_bounds__(256) void k_bnhead_apply(const SBnHeadArgs a) {
     }
   }
 }
+__global__ __launch_bounds__(256) void k_bnhead_apply(const SBnHeadArgs a) { bnhead_apply_body(a); }
+
+// The two forward passes with a slice coordinate (blockIdx.y): z [slices][N][C][HW], statistics, partials and pooled rows PER SLICE
+// -- the reference sends a trajectory's time slices through the norm one by one.  A slice's workgroups run the bodies above on that
+// slice's tensors: the chunking within a slice is what the plain launch picks for [N][C][HW], Chan's combine is per (slice, channel)
+// in the same tree, so every slice has the bits of its own plain call.  Forward only: no dropout scale.
+__device__ __forceinline__ SBnHeadArgs slice_of(SBnHeadArgs a) {
+  const size_t s = blockIdx.y;
+  a.z += s * (size_t)a.N * a.C * a.HW;
+  a.part += s * (size_t)a.nchunk * 2 * a.C;
+  a.stats += s * 2 * (size_t)a.C;
+  a.pooled += s * (size_t)a.N * a.C;
+  return a;
+}
+__global__ __launch_bounds__(256) void k_bnhead_stats_slices(const SBnHeadArgs a) { bnhead_stats_body(slice_of(a)); }
+__global__ __launch_bounds__(256) void k_bnhead_apply_slices(const SBnHeadArgs a) { bnhead_apply_body(slice_of(a)); }
 
 // dy of a plane's pixels: g_pooled scale / (H W) behind the ReLU mask, which is recomputed from xhat as the forward formed it
 __device__ __forceinline__ float head_gp(const SBnHeadArgs& a, int n, int c) {
@@ -223,6 +240,12 @@ static dim3 head_grid(const SBnHeadArgs& a) { return dim3((unsigned)(a.nchunk * 
 
 void launch_bnhead_stats(const SBnHeadArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bnhead_stats, head_grid(a), dim3(256), 0, s, a); }
 void launch_bnhead_apply(const SBnHeadArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bnhead_apply, head_grid(a), dim3(256), 0, s, a); }
+void launch_bnhead_stats_slices(const SBnHeadArgs& a, int slices, hipStream_t s) {
+  hipLaunchKernelGGL(k_bnhead_stats_slices, dim3((unsigned)(a.nchunk * a.C), (unsigned)slices), dim3(256), 0, s, a);
+}
+void launch_bnhead_apply_slices(const SBnHeadArgs& a, int slices, hipStream_t s) {
+  hipLaunchKernelGGL(k_bnhead_apply_slices, dim3((unsigned)(a.nchunk * a.C), (unsigned)slices), dim3(256), 0, s, a);
+}
 void launch_bnhead_bwd_stats(const SBnHeadArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bnhead_bwd_stats, head_grid(a), dim3(256), 0, s, a); }
 void launch_bnhead_bwd_dx(const SBnHeadArgs& a, hipStream_t s) { hipLaunchKernelGGL(k_bnhead_bwd_dx, head_grid(a), dim3(256), 0, s, a); }
 

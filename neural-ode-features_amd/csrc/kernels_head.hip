@@ -402,6 +402,178 @@ void launch_head_fwd(const node_shape& sh, const float* z, const float* gamma, c
   hipLaunchKernelGGL(k_head_fwd_g, dim3(sh.n), dim3(256), (size_t)sh.c * sizeof(float), s, z, gamma, beta, scale, pooled, stats,
                      sh.c, HW, sh.groups, sh.eps);
 }
+// ----------------------------------------------------------------------------
+// Distance of two trajectories behind the head's norm (reference adversarial/diff.py:111-123): per row (time slice, sample)
+//   ua = relu(GroupNorm(a)), ub = relu(GroupNorm(b));  out = { sqrt(sum (ub - ua)^2),  ua.ub / (max(|ua|, 1e-8) max(|ub|, 1e-8)) }
+// ua and ub are never written: the ATen chain writes and re-reads both [T N, C H W] tensors about ten times.  HBM bound: 2 x 64 KB
+// per row at [256, 8, 8], read once.  k_gn_relu_distance_v<LPC> is k_head_fwd_v's plan with both samples in registers (2 x 16
+// float4 per thread); k_gn_relu_distance_g is k_head_fwd_g's (one thread per channel, any geometry).  Group totals are added in
+// fp64 (G threads, cpg additions each: free) so that mean and 1/sigma are the rounded exact values of the fp32 channel sums, and
+// the row's four sums are fp64 from the element on (four fp64 multiply-adds per element pair, hidden behind 8 bytes of HBM): what
+// is left of the error is the fp32 normalisation itself.  The sums go lanes -> waves in one fixed order.  No atomics: the same bits
+// on every run.
+// ----------------------------------------------------------------------------
+namespace {
+// per-channel values of both samples chv[2][C] -> per-group totals grp[2][G], fp64 additions
+__device__ inline void groups_from_channels2(const float* chv, float* grp, int C, int G, int cpg) {
+  __syncthreads();
+  for (int j = threadIdx.x; j < 2 * G; j += blockDim.x) {
+    const int which = j / G, g = j - which * G;
+    double s = 0.0;
+    for (int k = 0; k < cpg; ++k) s += (double)chv[which * C + g * cpg + k];
+    grp[j] = (float)s;
+  }
+  __syncthreads();
+}
+// the row's four sums over the workgroup (lanes by xor butterflies, whose two operands commute, then the four waves in wave order)
+// and the two results; red: [16] doubles
+__device__ inline double wave_sum_f64(double v) {
+#pragma unroll
+  for (int m = 32; m > 0; m >>= 1) v += __shfl_xor(v, m);
+  return v;
+}
+__device__ inline void distance_finish(double dd, double ab, double aa, double bb, double* red, float* out2) {
+  dd = wave_sum_f64(dd); ab = wave_sum_f64(ab); aa = wave_sum_f64(aa); bb = wave_sum_f64(bb);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    red[w] = dd; red[4 + w] = ab; red[8 + w] = aa; red[12 + w] = bb;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const double sdd = (red[0] + red[1]) + (red[2] + red[3]), sab = (red[4] + red[5]) + (red[6] + red[7]);
+    const double saa = (red[8] + red[9]) + (red[10] + red[11]), sbb = (red[12] + red[13]) + (red[14] + red[15]);
+    out2[0] = (float)sqrt(sdd);
+    out2[1] = (float)(sab / (fmax(sqrt(saa), 1e-8) * fmax(sqrt(sbb), 1e-8)));     // F.cosine_similarity: each norm clamped at eps
+  }
+}
+}  // namespace
+
+template <int LPC>
+__global__ __launch_bounds__(256) void k_gn_relu_distance_v(const float* __restrict__ za, const float* __restrict__ zb,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ out, int C, int HW, int G, float eps) {
+  extern __shared__ double smd[];  // red[16] doubles, then chv[2][C], grp[2][G] (sums -> means), grp2[2][G] (centred squares)
+  double* red = smd;
+  float* chv = reinterpret_cast<float*>(smd + 16);
+  float* grp = chv + 2 * C;
+  float* grp2 = grp + 2 * G;
+  constexpr int CPP = 256 / LPC;
+  const int n = blockIdx.x, cpg = C / G;
+  const int lc = threadIdx.x / LPC, lq = threadIdx.x % LPC;
+  const int q4 = HW >> 2;                    // float4 per channel == LPC
+  const int iters = (C + CPP - 1) / CPP;
+  const float4* as = reinterpret_cast<const float4*>(za + (size_t)n * C * HW);
+  const float4* bs = reinterpret_cast<const float4*>(zb + (size_t)n * C * HW);
+  float4 va[HEAD_MAXIT], vb[HEAD_MAXIT];
+#pragma unroll
+  for (int i = 0; i < HEAD_MAXIT; ++i) {
+    const int c = i * CPP + lc;
+    const bool on = i < iters && c < C;
+    va[i] = on ? as[(size_t)c * q4 + lq] : make_float4(0.f, 0.f, 0.f, 0.f);
+    vb[i] = on ? bs[(size_t)c * q4 + lq] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const float inv_m = 1.0f / (float)(cpg * HW);
+#pragma unroll
+  for (int i = 0; i < HEAD_MAXIT; ++i) {
+    const int c = i * CPP + lc;
+    const float sa = lanes_sum<LPC>((va[i].x + va[i].y) + (va[i].z + va[i].w));
+    const float sb = lanes_sum<LPC>((vb[i].x + vb[i].y) + (vb[i].z + vb[i].w));
+    if (i < iters && c < C && lq == 0) { chv[c] = sa; chv[C + c] = sb; }
+  }
+  groups_from_channels2(chv, grp, C, G, cpg);
+#pragma unroll
+  for (int i = 0; i < HEAD_MAXIT; ++i) {
+    const int c = i * CPP + lc;
+    const bool on = i < iters && c < C;
+    const float ma = on ? grp[c / cpg] * inv_m : 0.f, mb = on ? grp[G + c / cpg] * inv_m : 0.f;
+    float a0 = va[i].x - ma, a1 = va[i].y - ma, a2 = va[i].z - ma, a3 = va[i].w - ma;
+    float b0 = vb[i].x - mb, b1 = vb[i].y - mb, b2 = vb[i].z - mb, b3 = vb[i].w - mb;
+    const float sa = lanes_sum<LPC>((a0 * a0 + a1 * a1) + (a2 * a2 + a3 * a3));
+    const float sb = lanes_sum<LPC>((b0 * b0 + b1 * b1) + (b2 * b2 + b3 * b3));
+    if (on && lq == 0) { chv[c] = sa; chv[C + c] = sb; }
+  }
+  groups_from_channels2(chv, grp2, C, G, cpg);
+  double dd = 0.0, ab = 0.0, aa = 0.0, bb = 0.0;
+#pragma unroll
+  for (int i = 0; i < HEAD_MAXIT; ++i) {
+    const int c = i * CPP + lc;
+    if (i < iters && c < C) {
+      const int g = c / cpg;
+      const float ma = grp[g] * inv_m, ra = 1.0f / sqrtf(grp2[g] * inv_m + eps);
+      const float mb = grp[G + g] * inv_m, rb = 1.0f / sqrtf(grp2[G + g] * inv_m + eps);
+      const float gm = gamma[c], bt = beta[c];
+      const float xa[4] = {va[i].x, va[i].y, va[i].z, va[i].w}, xb[4] = {vb[i].x, vb[i].y, vb[i].z, vb[i].w};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const float ua = fmaxf(((xa[k] - ma) * ra) * gm + bt, 0.f), ub = fmaxf(((xb[k] - mb) * rb) * gm + bt, 0.f);
+        const double da = (double)ua, db = (double)ub, d = db - da;
+        dd += d * d; ab += da * db; aa += da * da; bb += db * db;
+      }
+    }
+  }
+  distance_finish(dd, ab, aa, bb, red, out + (size_t)n * 2);
+}
+
+// any geometry: one thread per channel (cpg divides 256 or C <= 256, checked on the host: groups never straddle passes)
+__global__ __launch_bounds__(256) void k_gn_relu_distance_g(const float* __restrict__ za, const float* __restrict__ zb,
+                                                            const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            float* __restrict__ out, int C, int HW, int G, float eps) {
+  extern __shared__ double smd[];  // red[16] doubles, then chv[2][C], grp[2][G]
+  double* red = smd;
+  float* chv = reinterpret_cast<float*>(smd + 16);
+  float* grp = chv + 2 * C;
+  const int n = blockIdx.x, cpg = C / G;
+  const float inv_m = 1.0f / (float)(cpg * HW);
+  double dd = 0.0, ab = 0.0, aa = 0.0, bb = 0.0;
+  for (int cb = 0; cb < C; cb += 256) {
+    const int c = cb + threadIdx.x;
+    const bool on = c < C;
+    const int g = on ? c / cpg : 0;
+    const float* pa = za + ((size_t)n * C + (on ? c : 0)) * HW;
+    const float* pb = zb + ((size_t)n * C + (on ? c : 0)) * HW;
+    float sa = 0.f, sb = 0.f;
+    if (on)
+      for (int p = 0; p < HW; ++p) { sa += pa[p]; sb += pb[p]; }
+    __syncthreads();             // (the previous pass's readers of chv / grp are done)
+    if (on) { chv[c] = sa; chv[C + c] = sb; }
+    groups_from_channels2(chv, grp, C, G, cpg);      // (every pass recomputes all groups whose channels are written so far: G <= C)
+    const float ma = grp[g] * inv_m, mb = grp[G + g] * inv_m;
+    sa = 0.f; sb = 0.f;
+    if (on)
+      for (int p = 0; p < HW; ++p) { const float da = pa[p] - ma, db = pb[p] - mb; sa += da * da; sb += db * db; }
+    __syncthreads();
+    if (on) { chv[c] = sa; chv[C + c] = sb; }
+    groups_from_channels2(chv, grp, C, G, cpg);
+    const float ra = 1.0f / sqrtf(grp[g] * inv_m + eps), rb = 1.0f / sqrtf(grp[G + g] * inv_m + eps);
+    if (on) {
+      const float gm = gamma[c], bt = beta[c];
+      for (int p = 0; p < HW; ++p) {
+        const float ua = fmaxf(((pa[p] - ma) * ra) * gm + bt, 0.f), ub = fmaxf(((pb[p] - mb) * rb) * gm + bt, 0.f);
+        const double da = (double)ua, db = (double)ub, d = db - da;
+        dd += d * d; ab += da * db; aa += da * da; bb += db * db;
+      }
+    }
+  }
+  distance_finish(dd, ab, aa, bb, red, out + (size_t)n * 2);
+}
+
+void launch_gn_relu_distance(const node_shape& sh, const float* a, const float* b, const float* gamma, const float* beta, float* out,
+                             hipStream_t s) {
+  const int HW = sh.h * sh.w;
+  const size_t lds = 16 * sizeof(double) + (size_t)(2 * sh.c + 4 * sh.groups) * sizeof(float);
+#define DIST(LPC) hipLaunchKernelGGL((k_gn_relu_distance_v<LPC>), dim3(sh.n), dim3(256), lds, s, a, b, gamma, beta, out, sh.c, HW, sh.groups, sh.eps)
+  switch (head_lpc(sh)) {     // the head's own selection: H W % 4 != 0 (the 7 x 7 MNIST states) and samples too large for registers fall through
+    case 1: DIST(1); return;
+    case 4: DIST(4); return;
+    case 16: DIST(16); return;
+    case 64: DIST(64); return;
+    default: break;
+  }
+#undef DIST
+  hipLaunchKernelGGL(k_gn_relu_distance_g, dim3(sh.n), dim3(256), lds, s, a, b, gamma, beta, out, sh.c, HW, sh.groups, sh.eps);
+}
+
 // gsum[j] = sum_n gpart[n][j], j < 2 C: the per-sample (dgamma, dbeta) partials of a backward pass summed over the batch in
 // a fixed order (the caller's `gpart.sum(0)`: an ATen reduction launch + three indexing operators on the host)
 __global__ __launch_bounds__(256) void k_head_gsum(const float* __restrict__ gpart, float* __restrict__ gsum, int N, int W) {

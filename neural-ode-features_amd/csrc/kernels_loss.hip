@@ -34,6 +34,8 @@ struct LossArgs {
   float* loss;              // [1]
   float* stat;              // [2] or nullptr
   float* scratch;           // arrival counter (word 0; a FIXED place: launches of different batch sizes share the scratch), then [2 * nwg] partials from word 4
+                            // (k_head_loss_slices_fwd: one counter per slice from word 0, then [slices][2 * nwg] partials from word parts_off)
+  int parts_off;
   int N, C, O;
   int sum_reduction;
   int OL, G, NCH;           // class lanes per group (power of two <= 64), channel groups (64 / OL, or 1), 64-class chunks
@@ -54,7 +56,10 @@ __device__ __forceinline__ float wave_add(float v) {
 constexpr int LOSS_SPW = 4;   // samples per workgroup: one per wave
 
 // LDS: [wt: G * ((C / G) + 1) * OL * NCH floats (when w_lds)] [prow: 4 waves x (C + G)] [lrow: 4 waves x NCH * 64] [red: 16]
-__global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) {
+// `slice`: the rows [slice N, (slice + 1) N) of pooled / logits are this workgroup's batch (targets [N] shared by the slices), with a
+// counter, partials, loss and stat of its own -- 0 for the plain launch, blockIdx.y for k_head_loss_slices_fwd.  The operations on a
+// slice and their order do not depend on it.
+__device__ __forceinline__ void head_loss_fwd_body(const LossArgs& a, const unsigned slice) {
   extern __shared__ __align__(16) float lsm[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int C = a.C, O = a.O, OL = a.OL, G = a.G, NCH = a.NCH;
@@ -65,6 +70,7 @@ __global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) {
   float* red = lsm + (a.w_lds ? (size_t)G * (CG + 1) * OW : 0) + (size_t)LOSS_SPW * (C + G) + (size_t)LOSS_SPW * (NCH * 64);   // [9]
   const int n = blockIdx.x * LOSS_SPW + wave;
   const bool live = n < a.N;
+  const size_t row = (size_t)slice * a.N + n;
   const int g = lane / OL, ol = lane - g * OL;
 
   if (a.pooled != nullptr) {
@@ -76,7 +82,7 @@ __global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) {
       }
     }
     if (live)
-      for (int c = lane; c < C; c += 64) prow[c + c / CG] = a.pooled[(size_t)n * C + c];
+      for (int c = lane; c < C; c += 64) prow[c + c / CG] = a.pooled[row * C + c];
     __syncthreads();
     if (live) {
       for (int ch = 0; ch < NCH; ++ch) {
@@ -98,13 +104,13 @@ __global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) {
         for (int s = OL; s < 64; s <<= 1) acc += __shfl_xor(acc, s);     // over the channel groups (fixed order)
         if (o < O) acc += a.bias != nullptr ? a.bias[o] : 0.f;
         lrow[ch * 64 + lane] = (g == 0 && o < O) ? acc : -INFINITY;   // (lanes of the groups g > 0 are the slots >= OL: masked)
-        if (g == 0 && o < O) a.logits[(size_t)n * O + o] = acc;
+        if (g == 0 && o < O) a.logits[row * O + o] = acc;
       }
     }
   } else if (live) {
     for (int s = lane; s < NCH * 64; s += 64) {
       const int ch = s >> 6, o = ch * OL + (s & 63);
-      lrow[s] = ((s & 63) < OL && o < O) ? a.logits[(size_t)n * O + o] : -INFINITY;
+      lrow[s] = ((s & 63) < OL && o < O) ? a.logits[row * O + o] : -INFINITY;
     }
   }
   if (a.target == nullptr) return;
@@ -144,8 +150,8 @@ __global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) {
 #error "k_head_loss_fwd's fence-free hand-off is only valid on gfx950"
 #endif
   const unsigned nwg = gridDim.x;
-  unsigned* counter = reinterpret_cast<unsigned*>(a.scratch);
-  float* parts = a.scratch + 4;
+  unsigned* counter = reinterpret_cast<unsigned*>(a.scratch) + slice;
+  float* parts = a.scratch + a.parts_off + (size_t)slice * 2 * nwg;
   if (tid == 0) {
     const float pl = (red[0] + red[2]) + (red[4] + red[6]), ph = (red[1] + red[3]) + (red[5] + red[7]);
     __hip_atomic_store(parts + 2 * (size_t)blockIdx.x, pl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -168,11 +174,16 @@ __global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) {
   if (tid == 0) {
     const float tl = (red[0] + red[2]) + (red[4] + red[6]), th = (red[1] + red[3]) + (red[5] + red[7]);
     const float out = a.sum_reduction ? tl : tl / (float)a.N;
-    *a.loss = out;
-    if (a.stat != nullptr) { a.stat[0] = out; a.stat[1] = th; }
+    if (a.loss != nullptr) a.loss[slice] = out;
+    if (a.stat != nullptr) { a.stat[2 * (size_t)slice] = out; a.stat[2 * (size_t)slice + 1] = th; }
     __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch (stream order)
   }
 }
+
+__global__ __launch_bounds__(256) void k_head_loss_fwd(const LossArgs a) { head_loss_fwd_body(a, 0u); }
+// The same for every time slice of a trajectory: grid (ceil(N / 4), slices), so a workgroup's four samples never straddle two slices
+// and the last workgroup of a slice to arrive adds that slice's partials in k_head_loss_fwd's order.
+__global__ __launch_bounds__(256) void k_head_loss_slices_fwd(const LossArgs a) { head_loss_fwd_body(a, blockIdx.y); }
 
 struct LossBwdArgs {
   const float* pooled;       // [N][C] or nullptr (CE alone: only d_logits is produced)
@@ -318,6 +329,22 @@ __global__ __launch_bounds__(256) void k_head_loss_bwd(const LossBwdArgs a) {
   }
 }
 
+// lane map of a wave: OL class lanes x G channel groups (few classes: the C-long dot product is cut into 64 / OL pieces
+// that meet by shuffles), or all 64 lanes as class slots (NCH chunks of 64 classes, one channel group); depends on (C, O) alone, so
+// a trajectory's launch takes what a slice's launch takes.  false: the LDS row does not fit.
+bool loss_lane_map(LossArgs& a, size_t* lds_bytes) {
+  int OL = 1;
+  while (OL < a.O) OL *= 2;
+  if (a.pooled && OL <= 32 && a.C % (64 / OL) == 0) { a.OL = OL; a.G = 64 / OL; a.NCH = 1; }
+  else { a.OL = 64; a.G = 1; a.NCH = (a.O + 63) / 64; }
+  const size_t CG = a.pooled ? (size_t)a.C / a.G : 0, OW = (size_t)a.OL * a.NCH;
+  size_t wt_floats = a.pooled ? (size_t)a.G * (CG + 1) * OW : 0;
+  a.w_lds = a.pooled && wt_floats * sizeof(float) <= 96 * 1024;
+  if (!a.w_lds) wt_floats = 0;
+  *lds_bytes = (wt_floats + (size_t)LOSS_SPW * (a.C + a.G) + (size_t)LOSS_SPW * a.NCH * 64 + 16) * sizeof(float);
+  return *lds_bytes <= 150 * 1024;
+}
+
 int bad(int code, const char* msg) { return set_error(code, msg); }
 
 }  // namespace
@@ -342,24 +369,46 @@ int node_head_loss_fwd(const node_head_loss* h, void* stream) {
   if (h->target && (!h->loss || !h->scratch)) return bad(NODE_ERR_NULL, "target given without loss / scratch");
   LossArgs a;
   a.pooled = h->pooled; a.weight = h->weight; a.bias = h->bias; a.target = reinterpret_cast<const long long*>(h->target);
-  a.logits = h->logits; a.loss = h->loss; a.stat = h->stat; a.scratch = h->scratch;
+  a.logits = h->logits; a.loss = h->loss; a.stat = h->stat; a.scratch = h->scratch; a.parts_off = 4;
   a.N = h->n; a.C = h->pooled ? h->c : 0; a.O = h->classes; a.sum_reduction = h->reduction == NODE_REDUCE_SUM ? 1 : 0;
-  // lane map of a wave: OL class lanes x G channel groups (few classes: the C-long dot product is cut into 64 / OL pieces
-  // that meet by shuffles), or all 64 lanes as class slots (NCH chunks of 64 classes, one channel group)
-  int OL = 1;
-  while (OL < a.O) OL *= 2;
-  if (a.pooled && OL <= 32 && a.C % (64 / OL) == 0) { a.OL = OL; a.G = 64 / OL; a.NCH = 1; }
-  else { a.OL = 64; a.G = 1; a.NCH = (a.O + 63) / 64; }
-  const size_t CG = a.pooled ? (size_t)a.C / a.G : 0, OW = (size_t)a.OL * a.NCH;
-  size_t wt_floats = a.pooled ? (size_t)a.G * (CG + 1) * OW : 0;
-  a.w_lds = a.pooled && wt_floats * sizeof(float) <= 96 * 1024;
-  if (!a.w_lds) wt_floats = 0;
-  const size_t lds = (wt_floats + (size_t)LOSS_SPW * (a.C + a.G) + (size_t)LOSS_SPW * a.NCH * 64 + 16) * sizeof(float);
-  if (lds > 150 * 1024) return bad(NODE_ERR_UNSUPPORTED, "head loss: in_features too large for one wave's LDS row");
+  size_t lds;
+  if (!loss_lane_map(a, &lds)) return bad(NODE_ERR_UNSUPPORTED, "head loss: in_features too large for one wave's LDS row");
   static bool attr[MAX_DEVICES] = {};
   allow_full_lds(reinterpret_cast<const void*>(k_head_loss_fwd), attr);
   const int grid = (a.N + LOSS_SPW - 1) / LOSS_SPW;
   hipLaunchKernelGGL(k_head_loss_fwd, dim3(grid), dim3(256), lds, (hipStream_t)stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return bad(NODE_ERR_HIP, hipGetErrorString(e));
+  return NODE_OK;
+}
+
+// slices <= 65535 (grid y); counters padded to a multiple of four words
+static int loss_slices_parts_off(int slices) { return (slices + 3) & ~3; }
+
+size_t node_head_loss_slices_scratch_bytes(int slices, int n) {
+  if (slices <= 0 || slices > 65535 || n <= 0) return 0;
+  return ((size_t)loss_slices_parts_off(slices) + (size_t)slices * 2 * ((n + LOSS_SPW - 1) / LOSS_SPW)) * sizeof(float);
+}
+
+int node_head_loss_slices_fwd(const node_head_loss_slices* h, void* stream) {
+  if (!h) return bad(NODE_ERR_NULL, "node_head_loss_slices is NULL");
+  if (h->slices <= 0 || h->n <= 0 || h->classes <= 0) return bad(NODE_ERR_SHAPE, "slices, n and classes must be positive");
+  if (h->classes > 1024) return bad(NODE_ERR_UNSUPPORTED, "at most 1024 classes");
+  if (h->slices > 65535) return bad(NODE_ERR_UNSUPPORTED, "at most 65535 slices");
+  if (!h->logits) return bad(NODE_ERR_NULL, "logits is NULL");
+  if (h->pooled && (!h->weight || h->c <= 0)) return bad(NODE_ERR_NULL, "pooled given without weight / c");
+  if (!h->pooled && !h->target) return bad(NODE_ERR_ARG, "nothing to do: neither pooled (Linear) nor target (loss) given");
+  if (h->target && ((!h->loss && !h->stat) || !h->scratch)) return bad(NODE_ERR_NULL, "target given without loss / stat or without scratch");
+  LossArgs a;
+  a.pooled = h->pooled; a.weight = h->weight; a.bias = h->bias; a.target = reinterpret_cast<const long long*>(h->target);
+  a.logits = h->logits; a.loss = h->loss; a.stat = h->stat; a.scratch = h->scratch; a.parts_off = loss_slices_parts_off(h->slices);
+  a.N = h->n; a.C = h->pooled ? h->c : 0; a.O = h->classes; a.sum_reduction = 1;
+  size_t lds;
+  if (!loss_lane_map(a, &lds)) return bad(NODE_ERR_UNSUPPORTED, "head loss: in_features too large for one wave's LDS row");
+  static bool attr[MAX_DEVICES] = {};
+  allow_full_lds(reinterpret_cast<const void*>(k_head_loss_slices_fwd), attr);
+  const int grid = (a.N + LOSS_SPW - 1) / LOSS_SPW;
+  hipLaunchKernelGGL(k_head_loss_slices_fwd, dim3(grid, h->slices), dim3(256), lds, (hipStream_t)stream, a);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return bad(NODE_ERR_HIP, hipGetErrorString(e));
   return NODE_OK;

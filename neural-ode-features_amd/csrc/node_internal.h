@@ -543,6 +543,9 @@ int head_check(const node_shape* sh, char* why, size_t why_len);
 void launch_head_gsum(const float* gpart, float* gsum, int N, int C, hipStream_t s);
 void launch_head_fwd(const node_shape& sh, const float* z, const float* gamma, const float* beta, const float* scale,
                      float* pooled, float* stats, hipStream_t s);
+// out [n][2] = { |ub - ua|_2, cosine(ua, ub) } of u = relu(GroupNorm(.)) for the rows of two tensors a, b [n][c][h w] (one launch)
+void launch_gn_relu_distance(const node_shape& sh, const float* a, const float* b, const float* gamma, const float* beta, float* out,
+                             hipStream_t s);
 void launch_gn_relu_fwd(const node_shape& sh, const float* z, const float* gamma, const float* beta, int relu, float* out,
                         float* stats, hipStream_t s);
 void launch_gn_relu_bwd(const node_shape& sh, const float* z, const float* gamma, const float* beta, const float* stats,

@@ -242,6 +242,8 @@ def accuracy(args):
     """evaluate.py:207-305: the classifier's loss / accuracy at every time slice of ONE dense-output solve per batch."""
     import pandas as pd
     import torch.nn.functional as F
+    from .head import trajectory_loss
+    from .odenet import FCClassifier
     model, p, xte, yte = load_run(args.run)
     _needs_odenet(p, 'accuracy')
     if args.limit:
@@ -268,9 +270,15 @@ def accuracy(args):
             for x, y in _test_batches(xte, yte, p.batch_size, args.device):
                 pr = model(x)                                      # timestamps (T) x batch (N) x classes (C)
                 nfe_forward += model.nfe(reset=True)
-                losses = F.cross_entropy(pr.permute(1, 2, 0), y.unsqueeze(1).expand(-1, T), reduction='none')      # N x T
-                tot_losses += losses.sum(0).cpu()
-                n_correct += (y.unsqueeze(0).expand(T, -1) == pr.argmax(dim=-1)).sum(-1).float().cpu()
+                if FCClassifier.fused_trajectory:
+                    # every slice's summed loss and hit count: one launch and one read-back (head.trajectory_loss)
+                    stat = trajectory_loss(pr, y).cpu()
+                    tot_losses += stat[:, 0]
+                    n_correct += stat[:, 1]
+                else:       # the ATen chain, as before that kernel existed (A/B runs, tests)
+                    losses = F.cross_entropy(pr.permute(1, 2, 0), y.unsqueeze(1).expand(-1, T), reduction='none')      # N x T
+                    tot_losses += losses.sum(0).cpu()
+                    n_correct += (y.unsqueeze(0).expand(T, -1) == pr.argmax(dim=-1)).sum(-1).float().cpu()
                 n_processed += y.shape[0]
                 n_batches += 1
             frames.append(pd.DataFrame({'t1': t1.numpy(), 'test_loss': (tot_losses / n_processed).numpy(),

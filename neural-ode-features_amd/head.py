@@ -372,3 +372,109 @@ def linear_cross_entropy(pooled, weight, bias, target, reduction: str = 'mean'):
     loss, stat, logits = _LinearCrossEntropy.apply(pooled, weight, bias, target.contiguous(), _REDUCTIONS[reduction], None)
     loss.node_stat = stat
     return loss, logits
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The head of a whole trajectory [T, N, C, H, W] (the ODE block with `return_last_only = False`, model.py:39-40; the ResNet's
+# taps, model.py:99) in one call.  Behind a GroupNorm there is nothing to add: the norm is per sample, `head_pool` / `gn_relu` /
+# `linear` run one workgroup (one wave) per sample whatever the batch, and none of their launchers picks a kernel from n, so the
+# T N samples of the flattened VIEW come out with the bits of T calls (`FCClassifier.forward`).  BatchNorm's statistics are per
+# slice (the reference sends the slices through the norm one by one): `bn_head_pool_slices`.  The loss of the accuracy sweep
+# (evaluate.py:258-262) and the trajectory distance of `attack diff` (diff.py:111-123) are one launch each.
+# ---------------------------------------------------------------------------------------------------------------
+_SLICES_SCRATCH = {}
+
+
+def bn_head_slices_fusable(x: torch.Tensor, norm) -> bool:
+    """What `bn_head_pool_slices` takes: a contiguous trajectory [T, N, C, H, W] whose slices `bn_head_fusable` accepts, outside
+    autograd (the sliced entry is forward only)."""
+    return (torch.is_tensor(x) and x.dim() == 5 and 1 <= x.shape[0] <= 65535 and x.is_contiguous() and bn_head_fusable(x[0], norm)
+            and not (torch.is_grad_enabled() and (x.requires_grad or norm.weight.requires_grad or norm.bias.requires_grad)))
+
+
+def bn_head_pool_slices(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: float) -> torch.Tensor:
+    """pooled[t, n, c] = mean_px relu(BatchNorm(x[t])), batch statistics of every slice its own: `bn_head_pool(x[t])` for all t
+    in two launches (node_bnhead_fwd_slices), every slice the bits of its own call.  Forward only."""
+    lib = _lib.load()
+    T, n, c, h, w = x.shape
+    shape = _lib.NodeBnfuncShape(n, c, h, w, eps)
+    g, b = gamma.detach().contiguous(), beta.detach().contiguous()
+    with torch.cuda.device(x.device):
+        nbytes = lib.node_bnhead_slices_scratch_bytes(shape, T)
+        if nbytes == 0:
+            _lib.unsupported()
+        pooled = torch.empty(T, n, c, device=x.device, dtype=torch.float32)
+        stats = torch.empty(T, 2, c, device=x.device, dtype=torch.float32)
+        scratch = torch.empty(nbytes // 8, device=x.device, dtype=torch.float64)
+        _lib.check(lib.node_bnhead_fwd_slices(shape, T, _ptr(x), _ptr(g), _ptr(b), _ptr(pooled), _ptr(stats), _ptr(scratch),
+                                              torch.cuda.current_stream(x.device).cuda_stream))
+    return pooled
+
+
+def _slices_scratch(device, slices, n):
+    """Arrival counters + partials of the sliced loss: zero before the first use, left at zero by every launch; the counters'
+    extent depends on `slices`, so one buffer per (device, stream, slices)."""
+    lib = _lib.load()
+    need = lib.node_head_loss_slices_scratch_bytes(int(slices), int(n)) // 4
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream, int(slices))
+    buf = _SLICES_SCRATCH.get(key)
+    if buf is None or buf.numel() < need:
+        buf = torch.zeros(max(need, 1024), dtype=torch.float32, device=device)
+        _SLICES_SCRATCH[key] = buf
+    return buf
+
+
+def trajectory_loss(logits: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """[T, 2] = (summed cross-entropy, number of arg-max hits) of every slice of `logits` [T, N, classes] against the shared
+    `target` [N] (int64): what the accuracy sweep accumulates per batch (evaluate.py:258-262).  fp32 logits on a HIP device with
+    at most 1024 classes: ONE launch (node_head_loss_slices_fwd), every row the bits of `cross_entropy(logits[t], target,
+    reduction='sum')` and its `.node_stat`; anything else: the same quantities through PyTorch.  No gradient."""
+    if logits.dim() != 3 or target.dim() != 1 or target.shape[0] != logits.shape[1]:
+        raise ValueError('trajectory_loss: logits [T, N, classes] and target [N], got %s and %s' % (tuple(logits.shape), tuple(target.shape)))
+    T, n, o = logits.shape
+    if not (logits.is_cuda and logits.dtype == torch.float32 and 1 <= o <= 1024 and 1 <= T <= 65535 and n >= 1
+            and target.is_cuda and target.dtype == torch.int64):
+        with torch.no_grad():
+            loss = F.cross_entropy(logits.reshape(T * n, o), target.repeat(T), reduction='none').reshape(T, n).sum(1)
+            hits = (logits.argmax(-1) == target.unsqueeze(0)).sum(-1)
+            return torch.stack([loss, hits.to(loss.dtype)], 1)
+    lib = _lib.load()
+    lg, tg = logits.detach().contiguous(), target.contiguous()
+    stat = torch.empty(T, 2, dtype=torch.float32, device=lg.device)
+    with torch.cuda.device(lg.device):
+        h = _lib.NodeHeadLossSlices(T, n, 0, o, None, None, None, _ptr(tg), _ptr(lg), None, _ptr(stat),
+                                    _ptr(_slices_scratch(lg.device, T, n)))
+        _lib.check(lib.node_head_loss_slices_fwd(C.byref(h), torch.cuda.current_stream(lg.device).cuda_stream))
+    return stat
+
+
+def _distance_fusable(traj0, traj1, norm):
+    return (isinstance(norm, torch.nn.GroupNorm) and norm.affine and not norm._forward_hooks and not norm._forward_pre_hooks
+            and traj0.is_cuda and traj0.dtype == torch.float32 and traj1.dtype == torch.float32 and traj1.device == traj0.device
+            and traj0.shape[2] == norm.num_channels and traj0.numel() > 0
+            and all(p.is_cuda and p.dtype == torch.float32 and p.device == traj0.device for p in (norm.weight, norm.bias)))
+
+
+def trajectory_distance(traj0: torch.Tensor, traj1: torch.Tensor, norm):
+    """(l2, cos), each [T, N]: Euclidean distance and cosine similarity of `relu(norm(.))` of two raw solver trajectories
+    [T, N, C, H, W], flattened per (slice, sample) -- the two numbers per time point of adversarial/diff.py:111-123.  fp32
+    trajectories on a HIP device behind an affine `nn.GroupNorm`: ONE launch that reads each trajectory once and writes
+    neither normalised tensor (node_gn_relu_distance); anything else: the module chain of `diff.py`, slice by slice."""
+    if traj0.dim() != 5 or traj0.shape != traj1.shape:
+        raise ValueError('trajectory_distance: two trajectories [T, N, C, H, W] of one shape, got %s and %s'
+                         % (tuple(traj0.shape), tuple(traj1.shape)))
+    T, n, c, h, w = traj0.shape
+    if not _distance_fusable(traj0, traj1, norm):
+        with torch.no_grad():
+            u0 = torch.stack([F.relu(norm(v)) for v in traj0]).reshape(T, n, -1)
+            u1 = torch.stack([F.relu(norm(v)) for v in traj1]).reshape(T, n, -1)
+            return (u1 - u0).pow(2).sum(-1).sqrt(), F.cosine_similarity(u1, u0, dim=-1)
+    lib = _lib.load()
+    a, b = traj0.detach().contiguous(), traj1.detach().contiguous()
+    g, bt = norm.weight.detach().contiguous(), norm.bias.detach().contiguous()
+    out = torch.empty(T, n, 2, dtype=torch.float32, device=a.device)
+    shape = _lib.NodeShape(T * n, c, h, w, norm.num_groups, norm.eps)
+    with torch.cuda.device(a.device):
+        _lib.check(lib.node_gn_relu_distance(shape, _ptr(a), _ptr(b), _ptr(g), _ptr(bt), _ptr(out),
+                                             torch.cuda.current_stream(a.device).cuda_stream))
+    return out[..., 0], out[..., 1]

@@ -209,7 +209,10 @@ class FCClassifier(_Wrapped):
         """CUDA fp32 inputs take the fused HIP head (head.py: one launch forward, one backward; two each behind a
         `norm='batch'` BatchNorm2d that `head.bn_head_fusable` accepts) for everything in front of the last
         layer; anything else -- CPU tensors, a body someone has edited beyond what
-        `ODENet.to_features_extractor` does -- runs the plain module sequence."""
+        `ODENet.to_features_extractor` does -- runs the plain module sequence.  A trajectory [T, N, C, H, W] comes back as
+        [T, N, out] (or [T, N, C] without the classification layer), slice t what `forward(x[t])` returns."""
+        if x.dim() == 5:
+            return self._trajectory(x)
         body = list(self.module.children())
         fusable = (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and len(body) in (5, 6)
                    and isinstance(body[1], nn.ReLU)
@@ -233,6 +236,44 @@ class FCClassifier(_Wrapped):
         from .head import bn_head_fusable
         return self.fused_batch and bn_head_fusable(x, norm)
 
+    # a trajectory [T, N, C, H, W] through the head in ONE call (a GroupNorm head: the nodes of a batch on the flattened view, T N
+    # samples; a BatchNorm head: the sliced entry, statistics per slice); False: one call per slice, as before (A/B runs, tests)
+    fused_trajectory = True
+
+    def _trajectory_fusable(self, x):
+        """The whole trajectory in one call: a HIP fp32 trajectory through an unedited, unhooked body that draws no dropout mask
+        (the loop draws one mask per slice: the RNG stream must not change), and for a BatchNorm head what the forward-only sliced
+        entry takes.  Everything else keeps the loop over the slices."""
+        from .head import bn_head_slices_fusable
+        body = list(self.module.children())
+        if not (self.fused_trajectory and x.is_cuda and x.dtype == torch.float32 and x.shape[0] >= 1 and len(body) in (5, 6)
+                and isinstance(body[1], nn.ReLU) and isinstance(body[2], nn.AdaptiveAvgPool2d) and isinstance(body[-2], Flatten)
+                and (len(body) == 5 or isinstance(body[3], nn.Dropout))
+                and (isinstance(body[-1], nn.Linear) or (isinstance(body[-1], nn.Sequential) and len(body[-1]) == 0))):
+            return False
+        if any(m._forward_hooks or m._forward_pre_hooks for m in self.modules()):
+            return False
+        if self.training and len(body) == 6 and body[3].p > 0:
+            return False
+        if isinstance(body[0], nn.GroupNorm):
+            return body[0].affine
+        return self.fused_batch and bn_head_slices_fusable(x, body[0])
+
+    def _trajectory(self, x):
+        if not self._trajectory_fusable(x):
+            return torch.stack([self.forward(xi) for xi in x])
+        from .head import bn_head_pool_slices, linear
+        T, N = x.shape[:2]
+        norm, last = self.module[0], self.module[-1]
+        if isinstance(norm, nn.BatchNorm2d):
+            pooled = bn_head_pool_slices(x, norm.weight, norm.bias, norm.eps).reshape(T * N, -1)
+        else:
+            # GroupNorm is per sample and the head's kernels run one workgroup (the Linear layer: one wave) per sample, picked from
+            # (C, H W, out) alone: the T N samples of the view have the bits of T calls, and autograd goes through the same nodes
+            pooled = self.pooled(x.reshape(T * N, *x.shape[2:]))
+        out = linear(pooled, last.weight, last.bias) if isinstance(last, nn.Linear) else pooled
+        return out.reshape(T, N, -1)
+
     def pooled(self, x):
         """dropout(mean_px relu(norm(x))): everything in front of the Linear layer, one launch each way (GroupNorm) or two
         (BatchNorm: statistics across the batch)."""
@@ -244,6 +285,23 @@ class FCClassifier(_Wrapped):
         if isinstance(gn, nn.BatchNorm2d):
             return bn_head_pool(x, gn.weight, gn.bias, gn.eps, p=p, training=training)
         return head_pool(x, gn.weight, gn.bias, gn.num_groups, gn.eps, p=p, training=training)
+
+
+def head_on_trajectory(head, x):
+    """`torch.stack([head(xi) for xi in x])` for a trajectory x [T, N, C, H, W] (model.py:39-40, :99) with ONE call of the head
+    where it takes one: an `FCClassifier` (its `forward` decides what runs), or what `to_features_extractor(keep_pool=False)`
+    leaves of it, `nn.Sequential(GroupNorm, ReLU)`, as `head.gn_relu` on the flattened view (GroupNorm is per sample).  A head
+    with hooks of its own is called slice by slice, so that they see what they saw."""
+    hooked = head._forward_hooks or head._forward_pre_hooks
+    if isinstance(head, FCClassifier) and not hooked:
+        return head(x)
+    if (FCClassifier.fused_trajectory and not hooked and isinstance(head, nn.Sequential) and len(head) == 2
+            and isinstance(head[0], nn.GroupNorm) and head[0].affine and isinstance(head[1], nn.ReLU)
+            and x.is_cuda and x.dtype == torch.float32
+            and not any(m._forward_hooks or m._forward_pre_hooks for m in head)):
+        from .head import gn_relu
+        return gn_relu(x.reshape(-1, *x.shape[2:]), head[0]).reshape(x.shape)
+    return torch.stack([head(xi) for xi in x])
 
 
 class ODENet(nn.Module):
@@ -275,11 +333,11 @@ class ODENet(nn.Module):
             elif isinstance(self.classifier.module[-1], nn.Sequential):   # classification layer removed: pool only
                 f = torch.stack([fi.mean(-1).mean(-1) for fi in f])
             else:
-                f = torch.stack([self.classifier(fi) for fi in f])
+                f = head_on_trajectory(self.classifier, f)
             out.append(f)
         x = self.odeblock(x)
-        if x.dim() > 4:   # [T, N, C, H, W]: head applied per time slice (model.py:39-40)
-            x = torch.stack([self.classifier(xi) for xi in x])
+        if x.dim() > 4:   # [T, N, C, H, W]: the head of every time slice (model.py:39-40), in one call where the head takes one
+            x = head_on_trajectory(self.classifier, x)
         else:
             x = self.classifier(x)
         if not out:

@@ -19,7 +19,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import _lib, workspace
-from .odenet import FCClassifier, ResBlock, _Wrapped, _stem
+from .odenet import FCClassifier, ResBlock, _Wrapped, _stem, head_on_trajectory
 
 def _block_params(blk):
     return [blk.norm1.weight, blk.norm1.bias, blk.conv1.weight, blk.norm2.weight, blk.norm2.bias, blk.conv2.weight]
@@ -242,9 +242,14 @@ class ResidualTrunk(nn.Sequential):
 
     def forward_taps(self, x):
         """(output, [every block's output]): the fused node writes them in one forward; otherwise block by block."""
+        out, taps = self.forward_taps_stacked(x)
+        return out, (list(taps.unbind(0)) if torch.is_tensor(taps) else taps)
+
+    def forward_taps_stacked(self, x):
+        """`forward_taps` with the taps as the fused node writes them, ONE tensor [blocks, N, C, H, W] (a trajectory for the head:
+        no copy); the list of the blocks' outputs where the modules ran."""
         if self._takes_fused(x):
-            out, taps = self._fused(x, True)
-            return out, list(taps.unbind(0))
+            return self._fused(x, True)
         taps = []
         for blk in self:
             x = blk(x)
@@ -276,7 +281,11 @@ class ResNet(nn.Module):
     def forward(self, x):
         x = self.downsample(x)
         if self._extract_features:
-            _, taps = self.features.forward_taps(x)
+            _, taps = self.features.forward_taps_stacked(x)
+            if torch.is_tensor(taps):
+                # the fused trunk's taps are one tensor: two head calls (stem output, taps) instead of seven, and no copy of the taps
+                return torch.cat([head_on_trajectory(self.classifier, x.detach().unsqueeze(0)),
+                                  head_on_trajectory(self.classifier, taps.detach())])
             return torch.stack([self.classifier(f.detach()) for f in [x] + taps])
         return self.classifier(self.features(x))
 
