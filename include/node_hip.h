@@ -513,6 +513,26 @@ int node_stem_bwd(const node_stem_shape* shape, const node_stem_params* params, 
  * the parameter gradients are node_stem_bwd's bit for bit.  Same workspace contract as node_stem_bwd. */
 int node_stem_bwd_dx(const node_stem_shape* shape, const node_stem_params* params, const float* x, const float* grad_out,
                      const node_stem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+/* Diagnostics (host only, needs no GPU): the launch plan of node_stem_fwd / node_stem_bwd for a shape, in this process.
+ * One node_stem_gn_info per GroupNorm + ReLU launch, in the order of the tensors they normalise (block 1 norm1, norm2, block 2
+ * norm1, norm2): hw pixels per sample, channels, cpg channels per group, cb the channel block one workgroup holds in LDS,
+ * blocks_per_sample = channels / cb, grid = n * blocks_per_sample workgroups; the backward launch of the same norm has the same
+ * geometry and (2 hw cb + 1024) * 4 bytes of LDS, the forward (hw cb + 512) * 4.  takes_w4: the last convolution (and with it
+ * the fourth norm) runs through the F(4x4,3x3) pipeline instead, so gn[3] describes launches that do not happen and
+ * wgrad_nsplit[3] slabs nobody fills.  wgrad_nsplit / wgrad_rows_per_split [i]: the split-K plan of the weight gradient of
+ * b1_c1_w (with b1_ds_w), b1_c2_w, b2_c1_w (with b2_ds_w), b2_c2_w.  Returns what node_stem_fwd would return for the shape
+ * (NODE_ERR_SHAPE, NODE_ERR_UNSUPPORTED: the shapes node_stem_workspace_bytes answers with 0), with `out` zeroed. */
+typedef struct node_stem_gn_info {
+  int32_t hw, channels, cpg, cb, blocks_per_sample, grid;
+} node_stem_gn_info;
+typedef struct node_stem_info {
+  node_stem_gn_info gn[4];
+  int32_t takes_w4;
+  int32_t wgrad_nsplit[4];
+  int32_t wgrad_rows_per_split[4];
+} node_stem_info;
+int node_stem_describe(const node_stem_shape* shape, node_stem_info* out);
+
 /* Diagnostics (tests, tools): the transposed first layer alone on NCHW tensors.  w0: [64, in_ch, 3, 3];
  * dy: [n, 64, h - 2, w - 2]; d_x: [n, in_ch, h, w]; shape->filters and shape->eps are ignored; any h, w >= 3. */
 size_t node_stem_conv0_dgrad_workspace_bytes(const node_stem_shape* shape);
@@ -567,6 +587,9 @@ int node_trunk_fwd(const node_trunk_shape* shape, const node_trunk_block* blocks
                    int keep_for_backward, void* ws, size_t ws_bytes, void* stream);
 int node_trunk_bwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* grad_out,
                    const node_trunk_block_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+/* Diagnostics (host only, needs no GPU): the geometry of the trunk's GroupNorm + ReLU launches (node_stem_gn_info above; one
+ * record, every norm of the trunk has the same).  Returns what node_trunk_fwd would return for the shape, with `out` zeroed. */
+int node_trunk_describe(const node_trunk_shape* shape, node_stem_gn_info* out);
 
 /* The dynamics of an ODE block with norm = 'batch' -- model.py:326-348 with model.py:274:
  *     f(t, x) = norm3(conv2(t, relu(norm2(conv1(t, relu(norm1(x)))))))

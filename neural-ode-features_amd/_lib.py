@@ -38,7 +38,7 @@ EXPORTS = [
     'node_conv3x3_w4_workspace_bytes', 'node_conv3x3_w4', 'node_w4_split3', 'node_w4_pair_stats',
     'node_w4s_layout', 'node_w4s_layout_jobs', 'node_w4s_tmaps',
     'node_stem_workspace_bytes', 'node_stem_fwd', 'node_stem_bwd', 'node_stem_conv_workspace_bytes', 'node_stem_conv',
-    'node_stem_bwd_dx', 'node_stem_conv0_dgrad_workspace_bytes', 'node_stem_conv0_dgrad', 'node_attack_step', 'node_attack_judge',
+    'node_stem_bwd_dx', 'node_stem_describe', 'node_stem_conv0_dgrad_workspace_bytes', 'node_stem_conv0_dgrad', 'node_attack_step', 'node_attack_judge',
     'node_head_loss_scratch_bytes', 'node_head_loss_fwd', 'node_head_loss_bwd',
     'node_flat_workspace_bytes', 'node_flat_begin', 'node_flat_stage', 'node_flat_scalar', 'node_flat_initial_step',
     'node_flat_finish_step', 'node_flat_status_read',
@@ -46,7 +46,7 @@ EXPORTS = [
     'node_svm_workspace_bytes', 'node_svm_fit', 'node_svm_cv_score',
     'node_augment_batch', 'node_resize_batch', 'node_resize_table',
     'node_imgconv_workspace_bytes', 'node_imgconv_fwd', 'node_imgconv_bwd',
-    'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd',
+    'node_trunk_workspace_bytes', 'node_trunk_fwd', 'node_trunk_bwd', 'node_trunk_describe',
     'node_downconv_workspace_bytes', 'node_downconv_fwd', 'node_downconv_bwd',
     'node_convstem_workspace_bytes', 'node_convstem_fwd', 'node_convstem_bwd', 'node_convstem_bwd_dx',
     'node_ministem_workspace_bytes', 'node_ministem_fwd', 'node_ministem_bwd',
@@ -160,6 +160,33 @@ class NodeTrunkShape(C.Structure):
 
 class NodeTrunkBlock(C.Structure):          # node_trunk_block and node_trunk_block_grads share this layout
     _fields_ = [(k, C.c_void_p) for k in TRUNK_BLOCK_FIELDS]
+
+
+class NodeStemGnInfo(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ('hw', 'channels', 'cpg', 'cb', 'blocks_per_sample', 'grid')]
+
+
+class NodeStemInfo(C.Structure):
+    _fields_ = [('gn', NodeStemGnInfo * 4), ('takes_w4', C.c_int32), ('wgrad_nsplit', C.c_int32 * 4),
+                ('wgrad_rows_per_split', C.c_int32 * 4)]
+
+
+def stem_plan(n, in_ch, h, w, filters, eps=1e-5):
+    """The launch plan of the GroupNorm residual stem for an [n, in_ch, h, w] batch in this process (node_stem_describe): 'gn', four
+    dicts of node_stem_gn_info (block 1 norm1, norm2, block 2 norm1, norm2), 'takes_w4', and 'wgrad', four (nsplit, rows_per_split)
+    pairs (b1_c1_w, b1_c2_w, b2_c1_w, b2_c2_w).  Needs no GPU; raises NodeHipError for a shape the node refuses."""
+    info = NodeStemInfo()
+    check(load().node_stem_describe(C.byref(NodeStemShape(n, in_ch, h, w, filters, eps)), C.byref(info)))
+    return {'gn': [{k: getattr(g, k) for k, _ in g._fields_} for g in info.gn], 'takes_w4': bool(info.takes_w4),
+            'wgrad': [(info.wgrad_nsplit[i], info.wgrad_rows_per_split[i]) for i in range(4)]}
+
+
+def trunk_plan(n, c, h, w, blocks=1, eps=1e-5):
+    """The geometry of the GroupNorm trunk's norm launches for an [n, c, h, w] state (node_trunk_describe): dict of
+    node_stem_gn_info.  Needs no GPU; raises NodeHipError for a shape the node refuses."""
+    info = NodeStemGnInfo()
+    check(load().node_trunk_describe(C.byref(NodeTrunkShape(n, c, h, w, blocks, eps)), C.byref(info)))
+    return {k: getattr(info, k) for k, _ in info._fields_}
 
 
 BNFUNC_PARAM_FIELDS = ('norm1_w', 'norm1_b', 'conv1_w', 'conv1_b', 'norm2_w', 'norm2_b', 'conv2_w', 'conv2_b', 'norm3_w', 'norm3_b')
@@ -445,6 +472,8 @@ def load():
     lib.node_stem_conv.argtypes = [P(NodeConvGeom), i32, vp, vp, vp, vp, vp, sz, vp]
     lib.node_stem_bwd_dx.restype = i32
     lib.node_stem_bwd_dx.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, P(NodeStemParams), vp, vp, sz, vp]
+    lib.node_stem_describe.restype = i32
+    lib.node_stem_describe.argtypes = [P(NodeStemShape), P(NodeStemInfo)]
     lib.node_stem_conv0_dgrad_workspace_bytes.restype = sz
     lib.node_stem_conv0_dgrad_workspace_bytes.argtypes = [P(NodeStemShape)]
     lib.node_stem_conv0_dgrad.restype = i32
@@ -523,6 +552,8 @@ def load():
     lib.node_bnsolve_adjoint.restype = i32
     lib.node_bnsolve_adjoint.argtypes = [P(NodeBnfuncShape), P(NodeBnfuncParams), vp, vp, P(C.c_float), i32, f32, f32, i32,
                                          P(NodeBnsolveOpts), vp, P(NodeBnfuncParams), P(NodeStats), vp, sz, vp]
+    lib.node_trunk_describe.restype = i32
+    lib.node_trunk_describe.argtypes = [P(NodeTrunkShape), P(NodeStemGnInfo)]
     lib.node_trunk_bwd.restype = i32
     lib.node_trunk_bwd.argtypes = [P(NodeTrunkShape), P(NodeTrunkBlock), vp, P(NodeTrunkBlock), vp, vp, sz, vp]
     lib.node_bntrunk_workspace_bytes.restype = sz

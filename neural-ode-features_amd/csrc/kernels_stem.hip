@@ -3,7 +3,8 @@
 //   model.py:268-271 (GroupNorm(min(32, C), C)).
 // Round 3 ran these seven convolutions through MIOpen: 1.3 ms of the 5.5 ms cfg-2 step, a third of it layout transposes
 // and PyTorch reductions around the library's kernels.  Here the stem is NHWC from its first kernel to its last:
-//   k_stem_conv      forward convolutions and data gradients of the 64 / 256-channel layers: a gather GEMM over
+//   k_stem_conv      forward convolutions and data gradients of the 64 ... 4096-channel layers (the stems, the trunks, the 4x4
+//                    hand-off convolutions; reductions of more than 4096 products in segments: the SEG instance): a gather GEMM over
 //                    (tap, input channel) on the bf16 matrix pipe at fp32 accuracy -- both operands arrive as exact bf16
 //                    triples, staged global -> LDS by plain 16-B copies (LDS-DMA through a ring of stages), six
 //                    v_mfma_f32_32x32x16_bf16 per fp32 product block
@@ -121,14 +122,19 @@ __device__ __forceinline__ void ring_step(int q, int nq) {
 }
 
 // ============================================================================
-// k_stem_conv<KC, D>: out[row][co] = sum_{tap, ci} in[row @ tap][ci] * w[tap][co][ci]
+// k_stem_conv<KC, D, SEG>: out[row][co] = sum_{tap, ci} in[row @ tap][ci] * w[tap][co][ci]
 //   tile: 128 rows x 64 columns, four waves, wave w = rows 32 w .. 32 w + 31 x both 32-column blocks
 //   K chunk: one tap x KC input channels = KC / 16 MFMA K steps of six part products; both operands through the ring above
 //   (KC = 32: four stages of 36 KB, three in flight; KC = 64: two of 72 KB), one barrier per chunk
 //   a lane stages the same A rows for every chunk (row -> pixel decode once, source rows once per tap); a tap outside the
 //   image reads the zero row
+//   SEG (long reductions: launch_stem_conv): the accumulators take one segment of STEM_SEG_K products per output, then join a
+//   running total and start from zero.  One fp32 accumulator rounds once per MFMA: over the 9216 products of a 3x3 filter on 1024
+//   channels that chain came to 8 - 9 x the error of an fp32 CPU convolution (measured: tests/test_gpu_stem_geometry.py), growing
+//   with the square root of K; in segments it stays where K = 2048 has it.  SEG = false is the kernel without a total.
 // ============================================================================
-template <int KC, int D>
+constexpr int STEM_SEG_K = 2048;
+template <int KC, int D, bool SEG>
 __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
   constexpr int BM = 128, BN = 64, NST = D + 1, KS = KC / 16;
   constexpr int ROWB = 2 * KC, PP = KC / 8, RPI = 64 / PP, SH = KC == 64 ? 1 : 2;
@@ -298,8 +304,31 @@ __global__ __launch_bounds__(256) void k_stem_conv(const SConvArgs a) {
     st_fill = st_fill + 1 == NST ? 0 : st_fill + 1;
   };
   int q = 0;
-  for (; q + D < nchunk; ++q) step(q, std::true_type());
-  for (; q < nchunk; ++q) step(q, std::false_type());
+  if constexpr (SEG) {
+    constexpr int QSEG = STEM_SEG_K / KC;              // chunks per segment: the same K boundaries at every KC
+    f32x16 tot[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) tot[c][i] = 0.f;
+    auto join = [&]() {
+      if ((q + 1) % QSEG == 0 && q + 1 < nchunk) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+#pragma unroll
+          for (int i = 0; i < 16; ++i) { tot[c][i] += acc[c][i]; acc[c][i] = 0.f; }
+      }
+    };
+    for (; q + D < nchunk; ++q) { step(q, std::true_type()); join(); }
+    for (; q < nchunk; ++q) { step(q, std::false_type()); join(); }
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int i = 0; i < 16; ++i) acc[c][i] = tot[c][i] + acc[c][i];
+  } else {
+    for (; q + D < nchunk; ++q) step(q, std::true_type());
+    for (; q < nchunk; ++q) step(q, std::false_type());
+  }
 
   // epilogue: register r of a 32 x 32 block = row 8 (r / 4) + 4 (lane / 32) + r % 4, column lane % 32: 128-B row stores.
   // The conditions are decided once; every load of a lane is requested before the first is used (a row past the end reads
@@ -1376,15 +1405,23 @@ static bool stem_ring() { return env_int("NODE_TUNE_STEM_RING", 1) != 0; }
 void launch_stem_conv(const SConvArgs& a, hipStream_t s) {
   const int mt = a.cls_tile0[a.nclass];
   const int ntn = (a.Cout / 64) * ((a.mode == 0 && a.w2 != nullptr) ? 2 : 1);
-#define STEM_CONV(KC, D)                                                                  \
+#define STEM_CONV(KC, D, SEG)                                                             \
   {                                                                                       \
     static bool attr[MAX_DEVICES] = {};                                                   \
-    allow_full_lds(reinterpret_cast<const void*>(k_stem_conv<KC, D>), attr);              \
+    allow_full_lds(reinterpret_cast<const void*>(k_stem_conv<KC, D, SEG>), attr);         \
     const size_t lds = (size_t)(D + 1) * (3 * 128 + 3 * 64) * 2 * KC + 512;               \
-    hipLaunchKernelGGL((k_stem_conv<KC, D>), dim3(mt * ntn), dim3(256), lds, s, a);        \
+    hipLaunchKernelGGL((k_stem_conv<KC, D, SEG>), dim3(mt * ntn), dim3(256), lds, s, a);   \
   }
-  if (stem_ring()) STEM_CONV(32, STEM_RING_D)
-  else STEM_CONV(64, 1)
+  // reductions of more than two segments' length (3x3 on 512 channels and more, 4x4 on 512 and more) are summed in segments; every
+  // shorter one -- 3x3 on up to 256 channels: K <= 2304 -- runs the kernel without a total, the bits it always had
+  const bool seg = (size_t)a.KH * a.KW * a.Cin > 2 * STEM_SEG_K;
+  if (stem_ring()) {
+    if (seg) STEM_CONV(32, STEM_RING_D, true)
+    else STEM_CONV(32, STEM_RING_D, false)
+  } else {
+    if (seg) STEM_CONV(64, 1, true)
+    else STEM_CONV(64, 1, false)
+  }
 #undef STEM_CONV
 }
 

@@ -156,6 +156,25 @@ size_t node_stem_workspace_bytes(const node_stem_shape* shape) {
   return make_stem_plan(shape, nullptr).bytes;
 }
 
+int node_stem_describe(const node_stem_shape* shape, node_stem_info* out) {
+  if (!out) return fail(NODE_ERR_NULL, "out is NULL");
+  memset(out, 0, sizeof(*out));
+  const int rc = check_stem_shape(shape);
+  if (rc != NODE_OK) return rc;
+  const StemPlan p = make_stem_plan(shape, nullptr);
+  out->gn[0] = gn_info(p.N, p.H0 * p.W0, 64);      // the gn_args of node_stem_fwd / stem_bwd, in the forward's order
+  out->gn[1] = gn_info(p.N, p.H1 * p.W1, 64);
+  out->gn[2] = gn_info(p.N, p.H1 * p.W1, 64);
+  out->gn[3] = gn_info(p.N, p.H2 * p.W2, p.F);
+  out->takes_w4 = p.f4 ? 1 : 0;
+  const Wg* wg[4] = {&p.w1, &p.w2, &p.w3, &p.w4};
+  for (int i = 0; i < 4; ++i) {
+    out->wgrad_nsplit[i] = wg[i]->nsplit;
+    out->wgrad_rows_per_split[i] = wg[i]->rps;
+  }
+  return NODE_OK;
+}
+
 int node_stem_fwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, float* out, void* ws, size_t ws_bytes,
                   void* stream) {
   w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)

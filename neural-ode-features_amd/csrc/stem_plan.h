@@ -138,6 +138,16 @@ inline SGnArgs gn_args(const float* h, const float* gamma, const float* beta, fl
   return a;
 }
 
+// what launch_stem_gn_fwd / launch_stem_gn_bwd make of gn_args(.., N, HW, C, ..): the record of node_stem_describe / node_trunk_describe
+inline node_stem_gn_info gn_info(int N, int HW, int C) {
+  const SGnArgs a = gn_args(nullptr, nullptr, nullptr, nullptr, N, HW, C, 0.f);
+  node_stem_gn_info i;
+  i.hw = a.HW; i.channels = a.C; i.cpg = a.cpg; i.cb = a.CB;
+  i.blocks_per_sample = a.C / a.CB;
+  i.grid = a.N * (a.C / a.CB);
+  return i;
+}
+
 inline int launch_ok(const char* what) {
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(NODE_ERR_HIP, "launch of %s failed: %s", what, hipGetErrorString(e));

@@ -140,6 +140,15 @@ size_t node_trunk_workspace_bytes(const node_trunk_shape* shape, int keep_for_ba
   return make_trunk_plan(shape, keep_for_backward != 0, nullptr).bytes;
 }
 
+int node_trunk_describe(const node_trunk_shape* shape, node_stem_gn_info* out) {
+  if (!out) return fail(NODE_ERR_NULL, "out is NULL");
+  memset(out, 0, sizeof(*out));
+  const int rc = check_trunk_shape(shape);
+  if (rc != NODE_OK) return rc;
+  *out = gn_info(shape->n, shape->h * shape->w, shape->channels);      // the gn_args of node_trunk_fwd / node_trunk_bwd
+  return NODE_OK;
+}
+
 int node_trunk_fwd(const node_trunk_shape* shape, const node_trunk_block* blocks, const float* x, float* out, float* taps,
                    int keep_for_backward, void* ws, size_t ws_bytes, void* stream) {
   int rc = check_trunk_shape(shape);

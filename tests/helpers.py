@@ -787,3 +787,74 @@ def at_hip_solve(case, want_grad_t=True, grad_last_only=False, grad_out=None):
         st = (ctypes.c_int32 * 4)()
         _lib.check(_lib.load().node_w4_pair_stats(st))
     return dict(out=out.cpu(), gy=gy.cpu(), gp=gp.cpu(), gt=gt.cpu() if gt is not None else None, fwd=fs, bwd=bs, pair=list(st))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the stem's kernel family through the C ABI with a workspace of the caller's own (tests/test_gpu_stem_gn_paths.py,
+# tests/test_gpu_stem_geometry.py)
+# ---------------------------------------------------------------------------------------------------------------------------------
+def stem_family_gpu_run(kind, dims, mod, order, x, cot, with_dx=False):
+    """One forward and one backward of a node through the C ABI: outputs, gradients and the workspace's bytes, all on the CPU.
+    kind 'stem': dims (n, in_ch, h, w, filters), node_stem_fwd / node_stem_bwd -- and with `with_dx` node_stem_bwd_dx behind them on
+    the same workspace, into gradient tensors of its own ('dx', 'dxgrad00' ..., 'ws_bwd_dx').  kind 'trunk': dims (n, channels, h, w,
+    blocks), node_trunk_fwd / node_trunk_bwd ('dx' always).  Workspace, outputs and gradients start as 0xFF bytes (NaN in fp32 and
+    bf16); 'ws_fwd' / 'ws_bwd' are the WHOLE workspace behind the forward and behind the backward."""
+    from neural_ode_features_amd import _lib
+    C = ctypes
+    lib = _lib.load()
+    n, a, h, w, c = dims
+    m = copy.deepcopy(mod).cuda()
+    ps = [p.detach().contiguous() for p in order(m)]
+    xg, cg = x.cuda(), cot.cuda()
+    nan = lambda t: torch.full(t.shape, float('nan'), dtype=torch.float32, device='cuda')
+    grads = [nan(p) for p in ps]
+    out = nan(cg)
+    stream = torch.cuda.current_stream().cuda_stream
+    eps = float(m[1].norm1.eps if kind == 'stem' else m[0].norm1.eps)
+    if kind == 'stem':
+        shape = _lib.NodeStemShape(n, a, h, w, c, eps)
+        nbytes = lib.node_stem_workspace_bytes(C.byref(shape))
+    else:
+        shape = _lib.NodeTrunkShape(n, a, h, w, c, eps)
+        nbytes = lib.node_trunk_workspace_bytes(C.byref(shape), 1)
+    assert nbytes > 0, lib.node_last_error()
+    ws = torch.full((nbytes + 256,), 0xFF, dtype=torch.uint8, device='cuda')
+    wsp = (ws.data_ptr() + 255) & ~255
+    res = {}
+    if kind == 'stem':
+        struct = lambda ts: _lib.NodeStemParams(*[t.data_ptr() for t in ts])
+        _lib.check(lib.node_stem_fwd(C.byref(shape), C.byref(struct(ps)), xg.data_ptr(), out.data_ptr(), wsp, nbytes, stream))
+        torch.cuda.synchronize()
+        res['ws_fwd'] = ws.cpu()
+        _lib.check(lib.node_stem_bwd(C.byref(shape), C.byref(struct(ps)), xg.data_ptr(), cg.data_ptr(), C.byref(struct(grads)), wsp,
+                                     nbytes, stream))
+        if with_dx:
+            torch.cuda.synchronize()
+            res['ws_bwd'] = ws.cpu()
+            dx, grads2 = nan(xg), [nan(p) for p in ps]
+            _lib.check(lib.node_stem_bwd_dx(C.byref(shape), C.byref(struct(ps)), xg.data_ptr(), cg.data_ptr(), C.byref(struct(grads2)),
+                                            dx.data_ptr(), wsp, nbytes, stream))
+            torch.cuda.synchronize()
+            res['ws_bwd_dx'] = ws.cpu()
+            res['dx'] = dx
+            for i, g in enumerate(grads2):
+                res['dxgrad%02d' % i] = g
+    else:
+        def blocks(ts):
+            arr = (_lib.NodeTrunkBlock * c)()
+            for i in range(c):
+                arr[i] = _lib.NodeTrunkBlock(*[t.data_ptr() for t in ts[6 * i:6 * i + 6]])
+            return arr
+        dx = nan(xg)
+        _lib.check(lib.node_trunk_fwd(C.byref(shape), blocks(ps), xg.data_ptr(), out.data_ptr(), None, 1, wsp, nbytes, stream))
+        torch.cuda.synchronize()
+        res['ws_fwd'] = ws.cpu()
+        _lib.check(lib.node_trunk_bwd(C.byref(shape), blocks(ps), cg.data_ptr(), blocks(grads), dx.data_ptr(), wsp, nbytes, stream))
+        res['dx'] = dx
+    torch.cuda.synchronize()
+    if 'ws_bwd' not in res:
+        res['ws_bwd'] = ws.cpu()
+    res['out'] = out
+    for i, g in enumerate(grads):
+        res['grad%02d' % i] = g
+    return {k: v.cpu() for k, v in res.items()}

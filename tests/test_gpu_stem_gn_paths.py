@@ -79,53 +79,11 @@ def _cpu_run(mod, order, x, cot, dtype, want_dx):
 
 
 def _gpu_run(case, kind, mod, order, x, cot):
-    """One forward and one backward through the C ABI with a workspace of our own: outputs, gradients and the workspace's bytes."""
-    from neural_ode_features_amd import _lib
-    lib = _lib.load()
+    """One forward and one backward through the C ABI with a workspace of our own: outputs, gradients and the workspace's bytes
+    (tests/helpers.py: stem_family_gpu_run, shared with tests/test_gpu_stem_geometry.py)."""
+    from tests.helpers import stem_family_gpu_run
     _, a, b, c, N = CASES[case]
-    m = copy.deepcopy(mod).cuda()
-    ps = [p.detach().contiguous() for p in order(m)]
-    xg, cg = x.cuda(), cot.cuda()
-    nan = lambda t: torch.full(t.shape, float('nan'), dtype=torch.float32, device='cuda')
-    grads = [nan(p) for p in ps]
-    out = nan(cg)
-    stream = torch.cuda.current_stream().cuda_stream
-    eps = float(m[1].norm1.eps if kind == 'stem' else m[0].norm1.eps)
-    if kind == 'stem':
-        shape = _lib.NodeStemShape(N, a, b, b, c, eps)
-        nbytes = lib.node_stem_workspace_bytes(C.byref(shape))
-    else:
-        shape = _lib.NodeTrunkShape(N, a, b, b, c, eps)
-        nbytes = lib.node_trunk_workspace_bytes(C.byref(shape), 1)
-    assert nbytes > 0, lib.node_last_error()
-    ws = torch.full((nbytes + 256,), 0xFF, dtype=torch.uint8, device='cuda')
-    wsp = (ws.data_ptr() + 255) & ~255
-    res = {}
-    if kind == 'stem':
-        struct = lambda ts: _lib.NodeStemParams(*[t.data_ptr() for t in ts])
-        _lib.check(lib.node_stem_fwd(C.byref(shape), C.byref(struct(ps)), xg.data_ptr(), out.data_ptr(), wsp, nbytes, stream))
-        torch.cuda.synchronize()
-        res['ws_fwd'] = ws.cpu()
-        _lib.check(lib.node_stem_bwd(C.byref(shape), C.byref(struct(ps)), xg.data_ptr(), cg.data_ptr(), C.byref(struct(grads)), wsp,
-                                     nbytes, stream))
-    else:
-        def blocks(ts):
-            arr = (_lib.NodeTrunkBlock * c)()
-            for i in range(c):
-                arr[i] = _lib.NodeTrunkBlock(*[t.data_ptr() for t in ts[6 * i:6 * i + 6]])
-            return arr
-        dx = nan(xg)
-        _lib.check(lib.node_trunk_fwd(C.byref(shape), blocks(ps), xg.data_ptr(), out.data_ptr(), None, 1, wsp, nbytes, stream))
-        torch.cuda.synchronize()
-        res['ws_fwd'] = ws.cpu()
-        _lib.check(lib.node_trunk_bwd(C.byref(shape), blocks(ps), cg.data_ptr(), blocks(grads), dx.data_ptr(), wsp, nbytes, stream))
-        res['dx'] = dx
-    torch.cuda.synchronize()
-    res['ws_bwd'] = ws.cpu()
-    res['out'] = out
-    for i, g in enumerate(grads):
-        res['grad%02d' % i] = g
-    return {k: v.cpu() for k, v in res.items()}
+    return stem_family_gpu_run(kind, (N, a, b, b, c), mod, order, x, cot)
 
 
 def _results(case, monkeypatch):
@@ -187,9 +145,8 @@ def test_both_paths_match_fp64_within_eight_times_the_fp32_cpu_distance(case, mo
 
 
 def _gn_cb(hw, c, cpg):
-    """stem_gn_cb (csrc/kernels_stem.hip), restated: the library exports no probe for it, so what the host test below checks
-    against the LIBRARY is the refusal (workspace size 0) and the acceptance (> 0) of node_stem_workspace_bytes, which calls
-    stem_gn_cb; the divisibility assertions hold for this restatement of the rule, not for the C++ itself."""
+    """stem_gn_cb (csrc/kernels_stem.hip), restated; the host test below holds the restatement to the library's own answer
+    (node_stem_describe) and checks the refusal (workspace size 0) and the acceptance (> 0) of node_stem_workspace_bytes."""
     budget = 150 * 1024
     cb = 8
     while cb < cpg:
@@ -215,3 +172,5 @@ def test_channel_blocks_keep_whole_groups_and_refused_shapes_stay_refused():
             cb = _gn_cb(hw, c, cpg)
             assert cb >= 8 and c % cb == 0 and cb % cpg == 0 and 256 % cb == 0
             assert (2 * hw * cb + 1024) * 4 <= 160 * 1024           # the backward's two tiles and its scratch fit a CU's LDS
+        assert [g['cb'] for g in _lib.stem_plan(2, 3, 32, 32, filters)['gn']] == [_gn_cb(30 * 30, 64, 2), _gn_cb(15 * 15, 64, 2),
+                                                                                 _gn_cb(15 * 15, 64, 2), _gn_cb(8 * 8, filters, filters // 32)]
