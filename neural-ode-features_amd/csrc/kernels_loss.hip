@@ -165,6 +165,9 @@ __device__ __forceinline__ void head_loss_fwd_body(const LossArgs& a, const unsi
   for (unsigned i = tid; i < nwg; i += 256) {
     sl += __hip_atomic_load(parts + 2 * (size_t)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     sh += __hip_atomic_load(parts + 2 * (size_t)i + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // read once, by this thread alone: back to zero, so that the whole scratch (not the counters alone) is left as it was found
+    __hip_atomic_store(parts + 2 * (size_t)i, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(parts + 2 * (size_t)i + 1, 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   sl = wave_add(sl);
   sh = wave_add(sh);
