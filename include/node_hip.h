@@ -533,6 +533,44 @@ typedef struct node_stem_info {
 } node_stem_info;
 int node_stem_describe(const node_stem_shape* shape, node_stem_info* out);
 
+/* The residual stem above for images the resident GroupNorm passes refuse -- 64 x 64 inputs (tiny-imagenet-200, CIFAR-10 resized
+ * for the transfer evaluation): 62 x 62 = 3844 pixels behind the first layer.  The same plan, kernels, arguments and workspace
+ * contract as node_stem_fwd / node_stem_bwd / node_stem_bwd_dx (grads NULL in node_stem_banded_bwd_dx: the data-gradient chain
+ * alone, d_x the same bits); each of the four GroupNorm + ReLU passes is the resident launch where its (sample, channel block)
+ * fits the LDS and otherwise a BANDED pair of launches (csrc/kernels_stem_banded.hip): a workgroup takes (sample, band of band_px
+ * consecutive pixels, cb channels) and holds nothing of the tensor.  Forward: per-band (mean, centred second moment) of every group,
+ * then every workgroup merges its groups' partials with Chan's formula in band order and normalises its band.  Backward: per-band
+ * channel sums, then every workgroup adds them in band order and writes its band of the gradient.  No atomics, no workgroup waits
+ * for another, every sum in one order: the same bits on every run.  LDS per workgroup does not depend on the image.
+ *   n >= 1; in_ch <= 3; h, w >= 5, no upper limit; filters a power of two in [64, 4096]; EVERY tensor of the plan under 2^31
+ *   elements -- (n h0 w0 + 1) 64, (n h1 w1 + 1) 64, (n h2 w2 + 1) filters.  NODE_ERR_SHAPE / NODE_ERR_UNSUPPORTED as node_stem_fwd
+ *   returns them for the same defect; the workspace-size call returns 0 then.
+ * NODE_TUNE_STEM_BAND_PX (default 128): pixels per band.  NODE_TUNE_STEM_BANDED=all: every pass banded, whatever fits (tests, A/B).
+ * Both are read once per call and are part of the workspace layout: a backward runs under the values its forward ran under.
+ * The describe call (host only, needs no GPU): per norm the node_stem_gn_info of the launch that runs -- resident: node_stem_describe's
+ * record, banded = 0 and the other fields 0; banded: cb the banded passes' channel block (max(64, cpg)), blocks_per_sample =
+ * channels / cb, grid = n * bands_per_sample * blocks_per_sample, which is grid_first and grid_second, the grids of the two launches
+ * of either direction -- then takes_w4 (the fourth norm then runs inside the F(4x4,3x3) pipeline and is never banded) and the
+ * split-K plans as in node_stem_info.  Refusals leave `out` zeroed. */
+typedef struct node_stem_banded_gn_info {
+  node_stem_gn_info gn;
+  int32_t banded, band_px, bands_per_sample, grid_first, grid_second;
+} node_stem_banded_gn_info;
+typedef struct node_stem_banded_info {
+  node_stem_banded_gn_info gn[4];
+  int32_t takes_w4;
+  int32_t wgrad_nsplit[4];
+  int32_t wgrad_rows_per_split[4];
+} node_stem_banded_info;
+size_t node_stem_banded_workspace_bytes(const node_stem_shape* shape);
+int node_stem_banded_describe(const node_stem_shape* shape, node_stem_banded_info* out);
+int node_stem_banded_fwd(const node_stem_shape* shape, const node_stem_params* params, const float* x, float* out,
+                         void* ws, size_t ws_bytes, void* stream);
+int node_stem_banded_bwd(const node_stem_shape* shape, const node_stem_params* params, const float* x, const float* grad_out,
+                         const node_stem_grads* grads, void* ws, size_t ws_bytes, void* stream);
+int node_stem_banded_bwd_dx(const node_stem_shape* shape, const node_stem_params* params, const float* x, const float* grad_out,
+                            const node_stem_grads* grads, float* d_x, void* ws, size_t ws_bytes, void* stream);
+
 /* Diagnostics (tests, tools): the transposed first layer alone on NCHW tensors.  w0: [64, in_ch, 3, 3];
  * dy: [n, 64, h - 2, w - 2]; d_x: [n, in_ch, h, w]; shape->filters and shape->eps are ignored; any h, w >= 3. */
 size_t node_stem_conv0_dgrad_workspace_bytes(const node_stem_shape* shape);

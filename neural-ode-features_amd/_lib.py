@@ -61,6 +61,7 @@ EXPORTS = [
     'node_bndownconv_workspace_bytes', 'node_bndownconv_describe', 'node_bndownconv_fwd', 'node_bndownconv_bwd',
     'node_head_loss_slices_scratch_bytes', 'node_head_loss_slices_fwd', 'node_bnhead_slices_scratch_bytes', 'node_bnhead_fwd_slices',
     'node_gn_relu_distance',
+    'node_stem_banded_workspace_bytes', 'node_stem_banded_describe', 'node_stem_banded_fwd', 'node_stem_banded_bwd', 'node_stem_banded_bwd_dx',
 ]
 
 
@@ -178,6 +179,31 @@ def stem_plan(n, in_ch, h, w, filters, eps=1e-5):
     info = NodeStemInfo()
     check(load().node_stem_describe(C.byref(NodeStemShape(n, in_ch, h, w, filters, eps)), C.byref(info)))
     return {'gn': [{k: getattr(g, k) for k, _ in g._fields_} for g in info.gn], 'takes_w4': bool(info.takes_w4),
+            'wgrad': [(info.wgrad_nsplit[i], info.wgrad_rows_per_split[i]) for i in range(4)]}
+
+
+class NodeStemBandedGnInfo(C.Structure):
+    _fields_ = [('gn', NodeStemGnInfo)] + [(k, C.c_int32) for k in ('banded', 'band_px', 'bands_per_sample', 'grid_first', 'grid_second')]
+
+
+class NodeStemBandedInfo(C.Structure):
+    _fields_ = [('gn', NodeStemBandedGnInfo * 4), ('takes_w4', C.c_int32), ('wgrad_nsplit', C.c_int32 * 4),
+                ('wgrad_rows_per_split', C.c_int32 * 4)]
+
+
+def stem_banded_plan(n, in_ch, h, w, filters, eps=1e-5):
+    """The launch plan of the banded residual stem (node_stem_banded_describe) for an [n, in_ch, h, w] batch in this process: `stem_plan`'s
+    dict, every entry of 'gn' with 'banded' (bool), 'band_px', 'bands_per_sample', 'grid_first' and 'grid_second' on top of the
+    node_stem_gn_info fields of the launch that runs.  Needs no GPU; raises NodeHipError for a shape the node refuses."""
+    info = NodeStemBandedInfo()
+    check(load().node_stem_banded_describe(C.byref(NodeStemShape(n, in_ch, h, w, filters, eps)), C.byref(info)))
+    gn = []
+    for g in info.gn:
+        d = {k: getattr(g.gn, k) for k, _ in g.gn._fields_}
+        d.update(banded=bool(g.banded), band_px=g.band_px, bands_per_sample=g.bands_per_sample, grid_first=g.grid_first,
+                 grid_second=g.grid_second)
+        gn.append(d)
+    return {'gn': gn, 'takes_w4': bool(info.takes_w4),
             'wgrad': [(info.wgrad_nsplit[i], info.wgrad_rows_per_split[i]) for i in range(4)]}
 
 
@@ -474,6 +500,16 @@ def load():
     lib.node_stem_bwd_dx.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, P(NodeStemParams), vp, vp, sz, vp]
     lib.node_stem_describe.restype = i32
     lib.node_stem_describe.argtypes = [P(NodeStemShape), P(NodeStemInfo)]
+    lib.node_stem_banded_workspace_bytes.restype = sz
+    lib.node_stem_banded_workspace_bytes.argtypes = [P(NodeStemShape)]
+    lib.node_stem_banded_describe.restype = i32
+    lib.node_stem_banded_describe.argtypes = [P(NodeStemShape), P(NodeStemBandedInfo)]
+    lib.node_stem_banded_fwd.restype = i32
+    lib.node_stem_banded_fwd.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, vp, sz, vp]
+    lib.node_stem_banded_bwd.restype = i32
+    lib.node_stem_banded_bwd.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, P(NodeStemParams), vp, sz, vp]
+    lib.node_stem_banded_bwd_dx.restype = i32
+    lib.node_stem_banded_bwd_dx.argtypes = [P(NodeStemShape), P(NodeStemParams), vp, vp, P(NodeStemParams), vp, vp, sz, vp]
     lib.node_stem_conv0_dgrad_workspace_bytes.restype = sz
     lib.node_stem_conv0_dgrad_workspace_bytes.argtypes = [P(NodeStemShape)]
     lib.node_stem_conv0_dgrad.restype = i32

@@ -15,6 +15,7 @@
 //   k_stem_gn_*      GroupNorm + ReLU forward (writes the triples the next convolution reads) and backward
 //   k_stem_prep / k_stem_from_nchw / k_stem_to_nchw / k_stem_reduce   filter splits, boundary layouts, slab sums
 #include "stem.h"
+#include "stem_split.h"
 #include <type_traits>
 
 namespace node {
@@ -23,9 +24,6 @@ namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 // x = h + m + l exactly (3 x 8 significant bits; round-to-nearest-even at each level)
 __device__ __forceinline__ void split3(float x, bf16_t& h, bf16_t& m, bf16_t& l) {
@@ -38,21 +36,7 @@ __device__ __forceinline__ void split3(float x, bf16_t& h, bf16_t& m, bf16_t& l)
   m = __builtin_bit_cast(bf16_t, bm);
   l = __builtin_bit_cast(bf16_t, bl);
 }
-// eight consecutive channels -> three 16-B vectors (v_cvt_pk_bf16_f32 pairs)
-__device__ __forceinline__ void split8(const float4& p, const float4& q, u32x4& hh, u32x4& mm, u32x4& ll) {
-  const f32x2 v[4] = {{p.x, p.y}, {p.z, p.w}, {q.x, q.y}, {q.z, q.w}};
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bf16x2 h = __builtin_convertvector(v[i], bf16x2);
-    const f32x2 r = v[i] - __builtin_convertvector(h, f32x2);
-    const bf16x2 m = __builtin_convertvector(r, bf16x2);
-    const f32x2 r2 = r - __builtin_convertvector(m, f32x2);
-    const bf16x2 l = __builtin_convertvector(r2, bf16x2);
-    hh[i] = __builtin_bit_cast(unsigned, h);
-    mm[i] = __builtin_bit_cast(unsigned, m);
-    ll[i] = __builtin_bit_cast(unsigned, l);
-  }
-}
+// (split8, eight consecutive channels -> three 16-B vectors: stem_split.h)
 __device__ __forceinline__ float bf16_f(bf16_t v) { return __builtin_bit_cast(float, (unsigned)v << 16); }
 
 // ============================================================================

@@ -112,6 +112,23 @@ void launch_stem_gn_fwd(const SGnArgs& a, hipStream_t s);
 void launch_stem_gn_bwd(const SGnArgs& a, hipStream_t s);
 
 // ----------------------------------------------------------------------------
+// The same two passes for blocks that do not fit the LDS (kernels_stem_banded.hip): a workgroup takes (sample, band of band_px
+// consecutive pixels, CB channels) and holds nothing of the tensor; two launches per pass and direction, band partials in between.
+// Same inputs and outputs as the resident passes (no `skip`); g.CB is not read.
+// ----------------------------------------------------------------------------
+struct SGnBandArgs {
+  SGnArgs g;
+  int band_px;             // pixels per band (the last band of a sample may be shorter)
+  int nbands;              // bands per sample = ceil(HW / band_px)
+  int CB;                  // stem_gn_band_cb(C, cpg)
+  float* fpart;            // forward  [N][nbands][G][2]: the band's (mean, centred second moment) per group
+  float* bpart;            // backward [N][nbands][2][C]: the band's (sum dy xhat, sum dy) per channel
+};
+int stem_gn_band_cb(int C, int cpg);         // channel block of the banded passes: max(64, cpg) -- C, cpg powers of two, C >= 64
+void launch_stem_gn_banded_fwd(const SGnBandArgs& a, hipStream_t s);
+void launch_stem_gn_banded_bwd(const SGnBandArgs& a, hipStream_t s);
+
+// ----------------------------------------------------------------------------
 // layout / preparation / reductions
 // ----------------------------------------------------------------------------
 // filters -> triples in both operand layouts: wf[3][taps][co][ci], wd[3][taps][ci][co]; conv0's filter -> w0t[28][64] fp32;

@@ -5,6 +5,8 @@
 //                         conv 3x3/2 | conv 1x1/2 | GN+ReLU | conv 3x3 (+ shortcut) | NHWC -> NCHW
 // backward: NCHW -> NHWC (+ triples) | per convolution: data gradient (+ the shortcut's on top) and weight gradient (the
 //           shortcut's rides in the 3x3's launch) | per GroupNorm: backward pass | ONE reduction launch for every slab
+// node_stem_banded_*: the same plan and the same bodies without the pixel ceiling; a GroupNorm pass whose (sample, channel block)
+// does not fit the LDS is the banded pair of launches of kernels_stem_banded.hip, its band partials behind the plan's other pieces.
 #include "host_common.h"
 #include "stem.h"
 #include "stem_plan.h"
@@ -37,8 +39,25 @@ struct StemPlan {
   bool f4_b16;
   float *xh4, *rs4, *Va, *Vg, *M4, *Z4, *dU4, *U4[2], *dh3n;
   unsigned short* Ub4[2];
+  // the banded family (node_stem_banded_*): per norm, whether its two passes are the banded ones of kernels_stem_banded.hip, and
+  // their band partials.  node_stem_*: all false, nothing taken.
+  bool banded[4];
+  int band_px, nbands[4];
+  float *fpart[4], *bpart[4];
   size_t bytes;
 };
+
+// NODE_TUNE_STEM_BANDED=all: every GroupNorm pass of the banded family is banded (tests, A/B); unset: only those whose block does not
+// fit the LDS.  NODE_TUNE_STEM_BAND_PX: pixels per band.  Both are read per call and are part of the workspace layout: a backward
+// runs under the values its forward ran under.
+bool stem_band_all() {
+  const char* e = getenv("NODE_TUNE_STEM_BANDED");
+  return e && strcmp(e, "all") == 0;
+}
+int stem_band_px() {
+  const int p = env_int("NODE_TUNE_STEM_BAND_PX", 128);
+  return p < 1 ? 1 : p > (1 << 20) ? (1 << 20) : p;
+}
 
 bool stem_takes_w4(const node_stem_shape* sh) {
   if (env_int("NODE_TUNE_STEM_W4", 1) == 0) return false;       // 0: the stem's own gather-GEMM kernels for the last convolution too (A/B, tests)
@@ -46,7 +65,7 @@ bool stem_takes_w4(const node_stem_shape* sh) {
   return h2 == 8 && w2 == 8 && sh->filters % 128 == 0 && sh->n % 8 == 0 && 16 % (sh->filters / 32) == 0;
 }
 
-StemPlan make_stem_plan(const node_stem_shape* sh, void* base) {
+StemPlan make_stem_plan(const node_stem_shape* sh, void* base, bool banded_family = false) {
   StemPlan p;
   memset(&p, 0, sizeof(p));
   p.N = sh->n; p.Cin0 = sh->in_ch; p.H = sh->h; p.W = sh->w; p.F = sh->filters; p.eps = sh->eps;
@@ -123,6 +142,19 @@ StemPlan make_stem_plan(const node_stem_shape* sh, void* base) {
     }
     p.dh3n = b.take<float>((size_t)p.R2 * F);
   }
+  if (banded_family) {     // (behind everything else: the other pieces lie where node_stem_* has them)
+    const bool all = stem_band_all();
+    p.band_px = stem_band_px();
+    const int hw[4] = {p.H0 * p.W0, p.H1 * p.W1, p.H1 * p.W1, p.H2 * p.W2}, ch[4] = {64, 64, 64, F};
+    for (int i = 0; i < 4; ++i) {
+      const int groups = ch[i] < 32 ? ch[i] : 32;
+      p.banded[i] = (all || stem_gn_cb(hw[i], ch[i], ch[i] / groups) == 0) && !(i == 3 && p.f4);
+      if (!p.banded[i]) continue;
+      p.nbands[i] = (hw[i] + p.band_px - 1) / p.band_px;
+      p.fpart[i] = b.take<float>((size_t)p.N * p.nbands[i] * groups * 2);
+      p.bpart[i] = b.take<float>((size_t)p.N * p.nbands[i] * 2 * ch[i]);
+    }
+  }
   p.bytes = b.off + 256;
   return p;
 }
@@ -145,6 +177,152 @@ int check_stem_shape(const node_stem_shape* sh) {
                    "power-of-two channel block); got %d", sh->filters);
   }
   return NODE_OK;
+}
+
+// node_stem_banded_*: check_stem_shape without the pixel ceiling -- a GroupNorm pass whose block does not fit the LDS is banded --
+// and with every tensor of the plan under 2^31 elements
+int check_stem_banded_shape(const node_stem_shape* sh) {
+  if (!sh) return fail(NODE_ERR_NULL, "shape is NULL");
+  if (sh->n <= 0 || sh->in_ch <= 0 || sh->h < 5 || sh->w < 5 || sh->filters <= 0) return fail(NODE_ERR_SHAPE, "bad stem shape");
+  if (sh->in_ch > 3) return fail(NODE_ERR_UNSUPPORTED, "the stem's first layer takes in_ch <= 3 (got %d)", sh->in_ch);
+  const int F = sh->filters;
+  if (F < 64 || F > 4096 || (F & (F - 1)) != 0)
+    return fail(NODE_ERR_UNSUPPORTED, "the stem's GroupNorm passes take power-of-two filter counts in [64, 4096]; got %d", F);
+  const size_t n = (size_t)sh->n, lim = (size_t)1 << 31;
+  const size_t hw0 = (size_t)(sh->h - 2) * (sh->w - 2);
+  const size_t hw1 = (size_t)down2(sh->h - 2) * down2(sh->w - 2);
+  const size_t hw2 = (size_t)down2(down2(sh->h - 2)) * down2(down2(sh->w - 2));
+  // the largest of each family: the input, fp32 tensors and one plane of the triples (rows + 1) behind each of the three resolutions
+  if (hw0 >= lim || n * hw0 >= lim || n * sh->in_ch * sh->h * sh->w >= lim || (n * hw0 + 1) * 64 >= lim || (n * hw1 + 1) * 64 >= lim ||
+      (n * hw2 + 1) * F >= lim)
+    return fail(NODE_ERR_UNSUPPORTED, "stem tensors must stay under 2^31 elements");
+  return NODE_OK;
+}
+
+SGnBandArgs band_args(const StemPlan& p, int i, const SGnArgs& g) {
+  SGnBandArgs a;
+  memset(&a, 0, sizeof(a));
+  a.g = g;
+  a.band_px = p.band_px; a.nbands = p.nbands[i]; a.CB = stem_gn_band_cb(g.C, g.cpg);
+  a.fpart = p.fpart[i]; a.bpart = p.bpart[i];
+  return a;
+}
+// norm i of the plan (block 1 norm1, norm2, block 2 norm1, norm2): resident where its block fits, banded otherwise
+int run_gn_fwd(const StemPlan& p, int i, const SGnArgs& g, hipStream_t st) {
+  if (p.banded[i]) {
+    launch_stem_gn_banded_fwd(band_args(p, i, g), st);
+    return launch_ok("stem_gn_banded_fwd");
+  }
+  launch_stem_gn_fwd(g, st);
+  return launch_ok("stem_gn_fwd");
+}
+int run_gn_bwd(const StemPlan& p, int i, const SGnArgs& g, hipStream_t st) {
+  if (p.banded[i]) {
+    launch_stem_gn_banded_bwd(band_args(p, i, g), st);
+    return launch_ok("stem_gn_banded_bwd");
+  }
+  launch_stem_gn_bwd(g, st);
+  return launch_ok("stem_gn_bwd");
+}
+
+// node_stem_fwd (banded_family false) and node_stem_banded_fwd (true): one body, the shape check and the plan's per-norm decision differ
+int stem_fwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, float* out, void* ws, size_t ws_bytes,
+             void* stream, bool banded_family, const char* who) {
+  w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)
+  int rc = banded_family ? check_stem_banded_shape(shape) : check_stem_shape(shape);
+  if (rc != NODE_OK) return rc;
+  if (!prm || !x || !out || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  const float* const* pp = reinterpret_cast<const float* const*>(prm);
+  for (int i = 0; i < 16; ++i)
+    if (!pp[i]) return fail(NODE_ERR_NULL, "stem parameter %d is NULL", i);
+  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
+  StemPlan p = make_stem_plan(shape, ws, banded_family);
+  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
+  hipStream_t st = (hipStream_t)stream;
+  const int N = p.N, F = p.F;
+
+  SPrepArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  const Filt* fl[6] = {&p.c1, &p.c2, &p.d1, &p.c3, &p.c4, &p.d2};
+  const float* fw[6] = {prm->b1_c1_w, prm->b1_c2_w, prm->b1_ds_w, prm->b2_c1_w, prm->b2_c2_w, prm->b2_ds_w};
+  for (int i = 0; i < 6; ++i) pa.job[i] = {fw[i], fl[i]->wf, fl[i]->wd, fl[i]->Cout, fl[i]->Cin, fl[i]->taps};
+  pa.njobs = 6;
+  pa.w0 = prm->conv0_w; pa.w0t = p.w0t; pa.k0 = 9 * p.Cin0;
+  const Trip* tz[8] = {&p.a0, &p.a1, &p.a2, &p.a3, &p.g3, &p.dh3t, &p.dx1t, &p.dh1t};
+  for (int i = 0; i < 8; ++i) {
+    pa.zero[i] = tz[i]->p + (size_t)tz[i]->rows * tz[i]->C;
+    pa.zero_plane[i] = tz[i]->plane;
+    pa.zero_c[i] = tz[i]->C;
+  }
+  pa.nzero = 8;
+  if (F > 4096) return fail(NODE_ERR_UNSUPPORTED, "filters > 4096");
+  launch_stem_prep(pa, st);
+  if ((rc = launch_ok("stem_prep")) != NODE_OK) return rc;
+
+  launch_stem_conv0_fwd(x, p.w0t, prm->conv0_b, p.h0, N, p.Cin0, p.H, p.W, st);
+  if ((rc = launch_ok("stem_conv0_fwd")) != NODE_OK) return rc;
+  {   // block 1: relu(norm1(h0)) -> a0
+    SGnArgs g = gn_args(p.h0, prm->b1_n1_w, prm->b1_n1_b, p.stats[0], N, p.H0 * p.W0, 64, p.eps);
+    g.a3 = p.a0.p; g.a_plane = p.a0.plane;
+    if ((rc = run_gn_fwd(p, 0, g, st)) != NODE_OK) return rc;
+  }
+  {   // conv1 (3x3 / 2) and the shortcut (1x1 / 2) in one launch
+    SConvArgs c = conv_fwd_args(p.a0, p.c1, p.h1, N, p.H0, p.W0, p.H1, p.W1, 3, 2, 1);
+    c.w2 = p.d1.wf; c.w2_plane = p.d1.plane; c.out2 = p.s1;
+    launch_stem_conv(c, st);
+    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
+  }
+  {
+    SGnArgs g = gn_args(p.h1, prm->b1_n2_w, prm->b1_n2_b, p.stats[1], N, p.H1 * p.W1, 64, p.eps);
+    g.a3 = p.a1.p; g.a_plane = p.a1.plane;
+    if ((rc = run_gn_fwd(p, 1, g, st)) != NODE_OK) return rc;
+  }
+  {
+    SConvArgs c = conv_fwd_args(p.a1, p.c2, p.x1, N, p.H1, p.W1, p.H1, p.W1, 3, 1, 1);
+    c.res = p.s1;
+    launch_stem_conv(c, st);
+    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
+  }
+  {   // block 2
+    SGnArgs g = gn_args(p.x1, prm->b2_n1_w, prm->b2_n1_b, p.stats[2], N, p.H1 * p.W1, 64, p.eps);
+    g.a3 = p.a2.p; g.a_plane = p.a2.plane;
+    if ((rc = run_gn_fwd(p, 2, g, st)) != NODE_OK) return rc;
+  }
+  {
+    SConvArgs c = conv_fwd_args(p.a2, p.c3, p.h3, N, p.H1, p.W1, p.H2, p.W2, 3, 2, 1);
+    c.w2 = p.d2.wf; c.w2_plane = p.d2.plane; c.out2 = p.s2;
+    launch_stem_conv(c, st);
+    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
+  }
+  if (p.f4) {
+    W4PackJobs jobs;
+    memset(&jobs, 0, sizeof(jobs));
+    for (int i = 0; i < 2; ++i) {
+      jobs.w[i] = prm->b2_c2_w; jobs.u[i] = p.U4[i]; jobs.ub[i] = p.f4_b16 ? p.Ub4[i] : nullptr; jobs.dgrad[i] = i; jobs.plain[i] = 1;
+    }
+    launch_w4_pack(jobs, 2, F, st);
+    if ((rc = launch_ok("w4_pack")) != NODE_OK) return rc;
+    launch_w4s_stem_in(p.h3, prm->b2_n2_w, prm->b2_n2_b, p.eps, F / 32, p.xh4, p.rs4, p.Va, N, F, N, st);
+    if ((rc = launch_ok("w4s_stem_in")) != NODE_OK) return rc;
+    launch_w4_gemm(p.Va, p.U4[0], p.M4, nullptr, N, F, st, p.f4_b16 ? p.Ub4[0] : nullptr);
+    if ((rc = launch_ok("w4_gemm")) != NODE_OK) return rc;
+    launch_w4s_stem_out(p.M4, p.s2, out, N, F, st);
+    return launch_ok(who);
+  }
+  {
+    SGnArgs g = gn_args(p.h3, prm->b2_n2_w, prm->b2_n2_b, p.stats[3], N, p.H2 * p.W2, F, p.eps);
+    g.a3 = p.a3.p; g.a_plane = p.a3.plane;
+    if ((rc = run_gn_fwd(p, 3, g, st)) != NODE_OK) return rc;
+  }
+  {
+    SConvArgs c = conv_fwd_args(p.a3, p.c4, p.outn, N, p.H2, p.W2, p.H2, p.W2, 3, 1, 1);
+    c.res = p.s2;
+    launch_stem_conv(c, st);
+    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
+  }
+  launch_stem_to_nchw(p.outn, out, N, F, p.H2 * p.W2, st);
+  if ((rc = launch_ok("stem_to_nchw")) != NODE_OK) return rc;
+  return launch_ok(who);
 }
 
 }  // namespace
@@ -177,105 +355,7 @@ int node_stem_describe(const node_stem_shape* shape, node_stem_info* out) {
 
 int node_stem_fwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, float* out, void* ws, size_t ws_bytes,
                   void* stream) {
-  w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)
-  int rc = check_stem_shape(shape);
-  if (rc != NODE_OK) return rc;
-  if (!prm || !x || !out || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
-  const float* const* pp = reinterpret_cast<const float* const*>(prm);
-  for (int i = 0; i < 16; ++i)
-    if (!pp[i]) return fail(NODE_ERR_NULL, "stem parameter %d is NULL", i);
-  if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
-  StemPlan p = make_stem_plan(shape, ws);
-  if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
-  hipStream_t st = (hipStream_t)stream;
-  const int N = p.N, F = p.F;
-
-  SPrepArgs pa;
-  memset(&pa, 0, sizeof(pa));
-  const Filt* fl[6] = {&p.c1, &p.c2, &p.d1, &p.c3, &p.c4, &p.d2};
-  const float* fw[6] = {prm->b1_c1_w, prm->b1_c2_w, prm->b1_ds_w, prm->b2_c1_w, prm->b2_c2_w, prm->b2_ds_w};
-  for (int i = 0; i < 6; ++i) pa.job[i] = {fw[i], fl[i]->wf, fl[i]->wd, fl[i]->Cout, fl[i]->Cin, fl[i]->taps};
-  pa.njobs = 6;
-  pa.w0 = prm->conv0_w; pa.w0t = p.w0t; pa.k0 = 9 * p.Cin0;
-  const Trip* tz[8] = {&p.a0, &p.a1, &p.a2, &p.a3, &p.g3, &p.dh3t, &p.dx1t, &p.dh1t};
-  for (int i = 0; i < 8; ++i) {
-    pa.zero[i] = tz[i]->p + (size_t)tz[i]->rows * tz[i]->C;
-    pa.zero_plane[i] = tz[i]->plane;
-    pa.zero_c[i] = tz[i]->C;
-  }
-  pa.nzero = 8;
-  if (F > 4096) return fail(NODE_ERR_UNSUPPORTED, "filters > 4096");
-  launch_stem_prep(pa, st);
-  if ((rc = launch_ok("stem_prep")) != NODE_OK) return rc;
-
-  launch_stem_conv0_fwd(x, p.w0t, prm->conv0_b, p.h0, N, p.Cin0, p.H, p.W, st);
-  if ((rc = launch_ok("stem_conv0_fwd")) != NODE_OK) return rc;
-  {   // block 1: relu(norm1(h0)) -> a0
-    SGnArgs g = gn_args(p.h0, prm->b1_n1_w, prm->b1_n1_b, p.stats[0], N, p.H0 * p.W0, 64, p.eps);
-    g.a3 = p.a0.p; g.a_plane = p.a0.plane;
-    launch_stem_gn_fwd(g, st);
-    if ((rc = launch_ok("stem_gn_fwd")) != NODE_OK) return rc;
-  }
-  {   // conv1 (3x3 / 2) and the shortcut (1x1 / 2) in one launch
-    SConvArgs c = conv_fwd_args(p.a0, p.c1, p.h1, N, p.H0, p.W0, p.H1, p.W1, 3, 2, 1);
-    c.w2 = p.d1.wf; c.w2_plane = p.d1.plane; c.out2 = p.s1;
-    launch_stem_conv(c, st);
-    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
-  }
-  {
-    SGnArgs g = gn_args(p.h1, prm->b1_n2_w, prm->b1_n2_b, p.stats[1], N, p.H1 * p.W1, 64, p.eps);
-    g.a3 = p.a1.p; g.a_plane = p.a1.plane;
-    launch_stem_gn_fwd(g, st);
-    if ((rc = launch_ok("stem_gn_fwd")) != NODE_OK) return rc;
-  }
-  {
-    SConvArgs c = conv_fwd_args(p.a1, p.c2, p.x1, N, p.H1, p.W1, p.H1, p.W1, 3, 1, 1);
-    c.res = p.s1;
-    launch_stem_conv(c, st);
-    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
-  }
-  {   // block 2
-    SGnArgs g = gn_args(p.x1, prm->b2_n1_w, prm->b2_n1_b, p.stats[2], N, p.H1 * p.W1, 64, p.eps);
-    g.a3 = p.a2.p; g.a_plane = p.a2.plane;
-    launch_stem_gn_fwd(g, st);
-    if ((rc = launch_ok("stem_gn_fwd")) != NODE_OK) return rc;
-  }
-  {
-    SConvArgs c = conv_fwd_args(p.a2, p.c3, p.h3, N, p.H1, p.W1, p.H2, p.W2, 3, 2, 1);
-    c.w2 = p.d2.wf; c.w2_plane = p.d2.plane; c.out2 = p.s2;
-    launch_stem_conv(c, st);
-    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
-  }
-  if (p.f4) {
-    W4PackJobs jobs;
-    memset(&jobs, 0, sizeof(jobs));
-    for (int i = 0; i < 2; ++i) {
-      jobs.w[i] = prm->b2_c2_w; jobs.u[i] = p.U4[i]; jobs.ub[i] = p.f4_b16 ? p.Ub4[i] : nullptr; jobs.dgrad[i] = i; jobs.plain[i] = 1;
-    }
-    launch_w4_pack(jobs, 2, F, st);
-    if ((rc = launch_ok("w4_pack")) != NODE_OK) return rc;
-    launch_w4s_stem_in(p.h3, prm->b2_n2_w, prm->b2_n2_b, p.eps, F / 32, p.xh4, p.rs4, p.Va, N, F, N, st);
-    if ((rc = launch_ok("w4s_stem_in")) != NODE_OK) return rc;
-    launch_w4_gemm(p.Va, p.U4[0], p.M4, nullptr, N, F, st, p.f4_b16 ? p.Ub4[0] : nullptr);
-    if ((rc = launch_ok("w4_gemm")) != NODE_OK) return rc;
-    launch_w4s_stem_out(p.M4, p.s2, out, N, F, st);
-    return launch_ok("node_stem_fwd");
-  }
-  {
-    SGnArgs g = gn_args(p.h3, prm->b2_n2_w, prm->b2_n2_b, p.stats[3], N, p.H2 * p.W2, F, p.eps);
-    g.a3 = p.a3.p; g.a_plane = p.a3.plane;
-    launch_stem_gn_fwd(g, st);
-    if ((rc = launch_ok("stem_gn_fwd")) != NODE_OK) return rc;
-  }
-  {
-    SConvArgs c = conv_fwd_args(p.a3, p.c4, p.outn, N, p.H2, p.W2, p.H2, p.W2, 3, 1, 1);
-    c.res = p.s2;
-    launch_stem_conv(c, st);
-    if ((rc = launch_ok("stem_conv")) != NODE_OK) return rc;
-  }
-  launch_stem_to_nchw(p.outn, out, N, F, p.H2 * p.W2, st);
-  if ((rc = launch_ok("stem_to_nchw")) != NODE_OK) return rc;
-  return launch_ok("node_stem_fwd");
+  return stem_fwd(shape, prm, x, out, ws, ws_bytes, stream, false, "node_stem_fwd");
 }
 
 }  // extern "C"
@@ -284,9 +364,9 @@ namespace {
 // node_stem_bwd (gr given, d_x NULL) and node_stem_bwd_dx (d_x given; gr NULL: the data-gradient chain alone -- no weight-gradient,
 // no slab-reduction launch)
 int stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, const float* grad_out,
-             const node_stem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream, const char* who) {
+             const node_stem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream, const char* who, bool banded_family = false) {
   w4_refresh_tuning();     // (NODE_TUNE_W4_*: once per call)
-  int rc = check_stem_shape(shape);
+  int rc = banded_family ? check_stem_banded_shape(shape) : check_stem_shape(shape);
   if (rc != NODE_OK) return rc;
   if (!prm || !x || !grad_out || !ws) return fail(NODE_ERR_NULL, "a required pointer is NULL");
   const float* const* pp = reinterpret_cast<const float* const*>(prm);
@@ -294,7 +374,7 @@ int stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const fl
   for (int i = 0; i < 16; ++i)
     if (!pp[i] || (gr && !gp[i])) return fail(NODE_ERR_NULL, "stem parameter / gradient %d is NULL", i);
   if (((uintptr_t)ws) & 255) return fail(NODE_ERR_ARG, "workspace must be 256-byte aligned");
-  StemPlan p = make_stem_plan(shape, ws);
+  StemPlan p = make_stem_plan(shape, ws, banded_family);
   if (ws_bytes < p.bytes) return fail(NODE_ERR_WORKSPACE, "stem workspace too small: %zu < %zu", ws_bytes, p.bytes);
   hipStream_t st = (hipStream_t)stream;
   const int N = p.N, F = p.F;
@@ -339,8 +419,7 @@ int stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const fl
     {
       SGnArgs g = gn_args(p.h3, prm->b2_n2_w, prm->b2_n2_b, p.stats[3], N, HW2, F, p.eps);
       g.da = p.da3; g.dh = nullptr; g.dh3 = p.dh3t.p; g.dh_plane = p.dh3t.plane; g.gpart = p.gpart[3];
-      launch_stem_gn_bwd(g, st);
-      if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
+      if ((rc = run_gn_bwd(p, 3, g, st)) != NODE_OK) return rc;
     }
   }
   // block 2, conv1 (3x3 / 2, 64 -> F) + shortcut (1x1 / 2, 64 -> F): both read a2
@@ -357,8 +436,7 @@ int stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const fl
   {
     SGnArgs g = gn_args(p.x1, prm->b2_n1_w, prm->b2_n1_b, p.stats[2], N, HW1, 64, p.eps);
     g.da = p.da2; g.dh = nullptr; g.dh3 = p.dx1t.p; g.dh_plane = p.dx1t.plane; g.gpart = p.gpart[2];
-    launch_stem_gn_bwd(g, st);
-    if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
+    if ((rc = run_gn_bwd(p, 2, g, st)) != NODE_OK) return rc;
   }
   // block 1, conv2 (3x3, 64 -> 64): dx1 is the gradient of its output AND of the shortcut s1
   if (gr) {
@@ -370,8 +448,7 @@ int stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const fl
   {
     SGnArgs g = gn_args(p.h1, prm->b1_n2_w, prm->b1_n2_b, p.stats[1], N, HW1, 64, p.eps);
     g.da = p.da1; g.dh = nullptr; g.dh3 = p.dh1t.p; g.dh_plane = p.dh1t.plane; g.gpart = p.gpart[1];
-    launch_stem_gn_bwd(g, st);
-    if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
+    if ((rc = run_gn_bwd(p, 1, g, st)) != NODE_OK) return rc;
   }
   // block 1, conv1 (3x3 / 2) + shortcut (1x1 / 2): both read a0
   if (gr) {
@@ -387,8 +464,7 @@ int stem_bwd(const node_stem_shape* shape, const node_stem_params* prm, const fl
   {
     SGnArgs g = gn_args(p.h0, prm->b1_n1_w, prm->b1_n1_b, p.stats[0], N, HW0, 64, p.eps);
     g.da = p.da0; g.dh = p.dh0; g.dh3 = nullptr; g.gpart = p.gpart[0];
-    launch_stem_gn_bwd(g, st);
-    if ((rc = launch_ok("stem_gn_bwd")) != NODE_OK) return rc;
+    if ((rc = run_gn_bwd(p, 0, g, st)) != NODE_OK) return rc;
   }
   if (d_x) {   // the transposed first layer: dh0 -> the image
     launch_stem_conv0_dgrad(p.dh0, prm->conv0_w, d_x, N, p.Cin0, p.H, p.W, st);
@@ -434,6 +510,65 @@ int node_stem_bwd_dx(const node_stem_shape* shape, const node_stem_params* prm, 
                      const node_stem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream) {
   if (!d_x) return fail(NODE_ERR_NULL, "a required pointer is NULL");
   return stem_bwd(shape, prm, x, grad_out, gr, d_x, ws, ws_bytes, stream, "node_stem_bwd_dx");
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// node_stem_banded_*: the same plan and bodies; a GroupNorm pass whose block does not fit the LDS runs banded
+// ---------------------------------------------------------------------------------------------------------------
+size_t node_stem_banded_workspace_bytes(const node_stem_shape* shape) {
+  if (check_stem_banded_shape(shape) != NODE_OK) return 0;
+  return make_stem_plan(shape, nullptr, true).bytes;
+}
+
+int node_stem_banded_describe(const node_stem_shape* shape, node_stem_banded_info* out) {
+  if (!out) return fail(NODE_ERR_NULL, "out is NULL");
+  memset(out, 0, sizeof(*out));
+  const int rc = check_stem_banded_shape(shape);
+  if (rc != NODE_OK) return rc;
+  const StemPlan p = make_stem_plan(shape, nullptr, true);
+  const int hw[4] = {p.H0 * p.W0, p.H1 * p.W1, p.H1 * p.W1, p.H2 * p.W2}, ch[4] = {64, 64, 64, p.F};
+  for (int i = 0; i < 4; ++i) {
+    node_stem_banded_gn_info& o = out->gn[i];
+    if (!p.banded[i]) {      // the resident launch: node_stem_describe's record
+      o.gn = gn_info(p.N, hw[i], ch[i]);
+      continue;
+    }
+    const int cpg = ch[i] / (ch[i] < 32 ? ch[i] : 32), cb = stem_gn_band_cb(ch[i], cpg);
+    o.gn.hw = hw[i]; o.gn.channels = ch[i]; o.gn.cpg = cpg; o.gn.cb = cb;
+    o.gn.blocks_per_sample = ch[i] / cb;
+    o.gn.grid = p.N * p.nbands[i] * (ch[i] / cb);
+    o.banded = 1;
+    o.band_px = p.band_px;
+    o.bands_per_sample = p.nbands[i];
+    o.grid_first = o.grid_second = o.gn.grid;
+  }
+  out->takes_w4 = p.f4 ? 1 : 0;
+  const Wg* wg[4] = {&p.w1, &p.w2, &p.w3, &p.w4};
+  for (int i = 0; i < 4; ++i) {
+    out->wgrad_nsplit[i] = wg[i]->nsplit;
+    out->wgrad_rows_per_split[i] = wg[i]->rps;
+  }
+  return NODE_OK;
+}
+
+int node_stem_banded_fwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, float* out, void* ws,
+                         size_t ws_bytes, void* stream) {
+  return stem_fwd(shape, prm, x, out, ws, ws_bytes, stream, true, "node_stem_banded_fwd");
+}
+
+int node_stem_banded_bwd(const node_stem_shape* shape, const node_stem_params* prm, const float* x, const float* grad_out,
+                         const node_stem_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+  if (!gr) {
+    const int rc = check_stem_banded_shape(shape);
+    return rc != NODE_OK ? rc : fail(NODE_ERR_NULL, "a required pointer is NULL");
+  }
+  return stem_bwd(shape, prm, x, grad_out, gr, nullptr, ws, ws_bytes, stream, "node_stem_banded_bwd", true);
+}
+
+int node_stem_banded_bwd_dx(const node_stem_shape* shape, const node_stem_params* prm, const float* x, const float* grad_out,
+                            const node_stem_grads* gr, float* d_x, void* ws, size_t ws_bytes, void* stream) {
+  if (!d_x) return fail(NODE_ERR_NULL, "a required pointer is NULL");
+  return stem_bwd(shape, prm, x, grad_out, gr, d_x, ws, ws_bytes, stream, "node_stem_banded_bwd_dx", true);
 }
 
 // ---------------------------------------------------------------------------------------------------------------

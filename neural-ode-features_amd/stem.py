@@ -6,6 +6,10 @@ PyTorch reductions.  The module keeps the reference's sub-modules as parameter c
 tensors, non-fp32 inputs and geometries the kernels do not take run the plain module sequence (what the CPU baseline
 and the gloo tests use) -- on a HIP device with the library missing, the fused path raises.
 
+Images of more than 2400 pixels behind the first layer -- 64x64 inputs: tiny-imagenet-200, CIFAR-10 resized for the transfer
+evaluation -- are ONE node too: `_BandedStemFn` (`node_stem_banded_fwd / node_stem_banded_bwd`), the same plan with the GroupNorm
+passes that do not fit the LDS run in bands of pixels (csrc/kernels_stem_banded.hip).
+
 A stem built with `norm='batch'` (`nn.BatchNorm2d(C, track_running_stats=False)` in the four norm slots) is ONE node as well:
 `_BnStemFn` (`node_bnstem_fwd / node_bnstem_bwd`, csrc/bnstem_api.hip), the same launch plan around the BatchNorm passes of the
 batch-norm dynamics.
@@ -156,6 +160,78 @@ class _StemFn(torch.autograd.Function):
         return (d_x, None, *grads)
 
 
+_BANDED_WS = workspace.Carried(keep=1)      # (device, shape) -> the banded node's workspace whose backward has run
+
+
+class _BandedStemFn(torch.autograd.Function):
+    """`_StemFn` on node_stem_banded_fwd / node_stem_banded_bwd / node_stem_banded_bwd_dx: the stem on images past the resident
+    GroupNorm passes' 2400 pixels.  Same workspace discipline (its own pool), same one-backward rule."""
+
+    @staticmethod
+    def forward(ctx, x, eps, *params):
+        lib = _lib.load()
+        x = x.detach().contiguous()
+        n, cin, h, w = x.shape
+        filters = params[-1].shape[0]
+        shape = _lib.NodeStemShape(n, cin, h, w, filters, eps)
+        dev = x.device
+        ps = [p.detach().contiguous() for p in params]
+        with torch.cuda.device(dev):
+            nbytes = lib.node_stem_banded_workspace_bytes(C.byref(shape))
+            if nbytes == 0:
+                _lib.unsupported()
+            key = (dev.index, n, cin, h, w, filters)
+            ws = _BANDED_WS.take(key, dev, nbytes)
+            out = torch.empty(n, filters, _out_size(h), _out_size(w), dtype=torch.float32, device=dev)
+            wsp = workspace.aligned_ptr(ws)
+            _lib.check(lib.node_stem_banded_fwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), out.data_ptr(), wsp, nbytes,
+                                                torch.cuda.current_stream(dev).cuda_stream))
+        ctx.shape_args = (n, cin, h, w, filters, eps)
+        ctx.ws, ctx.nbytes, ctx.key = ws, nbytes, key
+        ctx.save_for_backward(x, *ps)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, grad_out):
+        if ctx.ws is None:
+            raise RuntimeError('the fused stem keeps its activations in a workspace that the first backward releases: '
+                               'a second backward through the same forward (retain_graph=True) is not supported')
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('ResidualStem: the fused backward does not run inside a stream capture')
+        lib = _lib.load()
+        x, *ps = ctx.saved_tensors
+        shape = _lib.NodeStemShape(*ctx.shape_args)
+        dev = x.device
+        grad_out = grad_out.contiguous()
+        if grad_out.dtype != torch.float32:
+            grad_out = grad_out.float()
+        if grad_out.data_ptr() % 16:
+            grad_out = grad_out.clone()
+        # parameter gradients: all sixteen or none (an attack freezes the parameters: the data-gradient chain alone)
+        want_params = any(ctx.needs_input_grad[2:])
+        want_dx = ctx.needs_input_grad[0]     # (only with ResidualStem.input_grad: `banded_fusable` sends any other such input elsewhere)
+        ws = ctx.ws
+        d_x = None
+        with torch.cuda.device(dev):
+            grads = [torch.empty_like(p) for p in ps] if want_params or not want_dx else None
+            wsp = workspace.aligned_ptr(ws)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            if want_dx:
+                d_x = torch.empty_like(x)
+                _lib.check(lib.node_stem_banded_bwd_dx(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                                       C.byref(_struct(grads)) if grads is not None else None, d_x.data_ptr(), wsp,
+                                                       ctx.nbytes, stream))
+            else:
+                _lib.check(lib.node_stem_banded_bwd(C.byref(shape), C.byref(_struct(ps)), x.data_ptr(), grad_out.data_ptr(),
+                                                    C.byref(_struct(grads)), wsp, ctx.nbytes, stream))
+        _BANDED_WS.give(ctx.key, ws)        # free for the next forward of this shape (stream-ordered behind this backward)
+        ctx.ws = None
+        if grads is None:
+            grads = [None] * len(ps)
+        return (d_x, None, *grads)
+
+
 def _out_size(h):
     return ((h - 2 - 1) // 2 + 1 - 1) // 2 + 1
 
@@ -269,8 +345,9 @@ def bn_fusable(seq, x, input_grad=False) -> bool:
 
 def fusable(seq, x, input_grad=False) -> bool:
     """What the library's stem kernels take (node_stem_fwd): fp32 on a HIP device, in_ch <= 3, filters a power of two >= 64,
-    images of up to 2400 pixels behind the first layer (the GroupNorm passes hold a (sample, 8 channels) block in LDS);
-    anything else -- the 24- and 32-filter toy nets of the tests, 64x64 inputs -- runs the module sequence."""
+    images of up to 2400 pixels behind the first layer (the GroupNorm passes hold a (sample, 8 channels) block in LDS).
+    Larger images -- 64x64 inputs -- are `banded_fusable`'s; anything else -- the 24- and 32-filter toy nets of the tests --
+    runs the module sequence."""
     if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.shape[1] <= 3
             and min(x.shape[2], x.shape[3]) >= 5 and (x.shape[2] - 2) * (x.shape[3] - 2) <= 2400):
         return False
@@ -286,6 +363,32 @@ def fusable(seq, x, input_grad=False) -> bool:
             and all(p.is_cuda and p.dtype == torch.float32 for p in ps))
 
 
+def banded_fusable(seq, x, input_grad=False) -> bool:
+    """What node_stem_banded_fwd takes: `fusable`'s conditions without the pixel ceiling -- an fp32 NCHW batch on a HIP device,
+    n >= 1, in_ch <= 3, h, w >= 5; a stem `_params_of` recognises with filters a power of two in [64, 4096], fp32 parameters on the
+    input's device; an input that requires a gradient only with `input_grad` -- and on top of them: every tensor of the plan under
+    2^31 elements, 16-byte aligned tensors, no hooks on the stem's sub-modules (the node would not call them), no stream capture.
+    Anything else runs the module sequence."""
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and 1 <= x.shape[1] <= 3 and x.shape[0] >= 1
+            and min(x.shape[2], x.shape[3]) >= 5):
+        return False
+    ps = _params_of(seq)
+    if ps is None or _hooked(seq):
+        return False
+    if x.requires_grad and torch.is_grad_enabled() and not input_grad:
+        return False
+    n, cin, h, w = x.shape
+    filters = ps[-1].shape[0]
+    h1, w1 = (h - 2 - 1) // 2 + 1, (w - 2 - 1) // 2 + 1
+    if not (64 <= filters <= 4096 and filters & (filters - 1) == 0 and ps[0].shape[1] == cin
+            and (n * (h - 2) * (w - 2) + 1) * 64 < 2 ** 31 and (n * h1 * w1 + 1) * 64 < 2 ** 31
+            and (n * _out_size(h) * _out_size(w) + 1) * filters < 2 ** 31 and n * cin * h * w < 2 ** 31):
+        return False
+    if not all(p.is_cuda and p.dtype == torch.float32 and p.device == x.device and p.data_ptr() % 16 == 0 for p in ps):
+        return False
+    return x.data_ptr() % 16 == 0 and not torch.cuda.is_current_stream_capturing()
+
+
 class ResidualStem(nn.Sequential):
     """`nn.Sequential(Conv2d(in_ch, 64, 3, 1), ResBlock(64, 64, 2, conv1x1), ResBlock(64, out_ch, 2, conv1x1))` with the
     reference's state_dict keys; on a HIP device its forward and backward are the library's (one autograd node).
@@ -299,6 +402,10 @@ class ResidualStem(nn.Sequential):
     # node existed (A/B runs, tests).  GroupNorm stems do not read it.  `eval()` changes nothing: without running statistics the
     # reference normalises with the batch's statistics in evaluation too.
     fused_batch = True
+    # GroupNorm stems on images past the resident passes' 2400 pixels (64x64 inputs) as one node (`_BandedStemFn`,
+    # node_stem_banded_*); False: the module sequence, as before that node existed (A/B runs, tests).  Shapes `fusable` takes never
+    # read it.
+    fused_banded = True
 
     def forward(self, x):
         if _is_batch(self) and self.fused_batch and bn_fusable(self, x, self.input_grad):
@@ -307,9 +414,13 @@ class ResidualStem(nn.Sequential):
             if not keep:
                 ps = [p.detach() for p in ps]
             return _BnStemFn.apply(x, float(self[1].norm1.eps), keep, *ps)
-        if not fusable(self, x, self.input_grad):
+        if fusable(self, x, self.input_grad):
+            fn = _StemFn
+        elif self.fused_banded and banded_fusable(self, x, self.input_grad):
+            fn = _BandedStemFn
+        else:
             return super().forward(x)
         ps = _params_of(self)
         if not (torch.is_grad_enabled() and any(p.requires_grad for p in ps)):
-            return _StemFn.apply(x, float(self[1].norm1.eps), *[p.detach() for p in ps])
-        return _StemFn.apply(x, float(self[1].norm1.eps), *ps)
+            return fn.apply(x, float(self[1].norm1.eps), *[p.detach() for p in ps])
+        return fn.apply(x, float(self[1].norm1.eps), *ps)
