@@ -24,7 +24,7 @@ DIAG_SOURCES = ['kernels_w4_bf16.hip', 'kernels_w4_f16.hip', 'w4_select.hip', 'k
 SOURCES = ['kernels_layout.hip', 'kernels_groupnorm.hip', 'kernels_step_control.hip', 'kernels_generic.hip', 'kernels_theta_finalize.hip',
            'kernels_conv_direct.hip', 'kernels_conv_wino1d.hip', 'kernels_conv_wino2d.hip', 'kernels_conv_small.hip', 'conv_select.hip', 'kernels_wgrad.hip', 'kernels_head.hip', 'kernels_loss.hip', 'kernels_optim.hip', 'kernels_w4_pack.hip', 'kernels_w4_f32.hip', 'kernels_w4_bf16.hip', 'kernels_w4_f16.hip', 'kernels_w4_wgrad.hip', 'w4_select.hip', 'kernels_w4s.hip', 'kernels_stem.hip', 'kernels_stem_banded.hip', 'kernels_tiny.hip', 'kernels_tiny_solve.hip', 'kernels_retrieval.hip', 'kernels_svm.hip', 'kernels_augment.hip', 'kernels_resize.hip', 'kernels_imgconv.hip', 'kernels_pool.hip', 'kernels_ministem.hip', 'kernels_bnministem.hip', 'kernels_attack.hip', 'kernels_batchnorm.hip', 'kernels_bnhead.hip', 'bnfunc_api.hip', 'bnsolve_api.hip', 'bntrunk_api.hip', 'bnstem_api.hip', 'bnhead_api.hip', 'attack_api.hip', 'stem_api.hip', 'trunk_api.hip', 'downconv_api.hip', 'convstem_api.hip', 'bndownconv_api.hip', 'bnconvstem_api.hip','ministem_api.hip', 'bnministem_api.hip', 'retrieval_api.hip', 'svm_api.hip', 'augment_api.hip', 'resize_api.hip', 'imgconv_api.hip', 'pool_api.hip', 'host_common.hip', 'dims.hip', 'plan.hip', 'solver.hip', 'api_solve.hip',
            'api_backprop.hip', 'api_flat.hip', 'api_misc.hip']
-HEADERS = [os.path.join(CSRC, 'node_internal.h'), os.path.join(CSRC, 'wino4.h'), os.path.join(CSRC, 'w4_gemm.h'), os.path.join(CSRC, 'theta_finalize.h'), os.path.join(CSRC, 'w4s_pass_body.inc'), os.path.join(CSRC, 'conv_common.h'), os.path.join(CSRC, 'pointwise_common.h'), os.path.join(CSRC, 'stem.h'), os.path.join(CSRC, 'stem_split.h'), os.path.join(CSRC, 'batchnorm.h'), os.path.join(CSRC, 'bnfunc.h'), os.path.join(CSRC, 'attack.h'), os.path.join(CSRC, 'stem_plan.h'), os.path.join(CSRC, 'ministem.h'), os.path.join(CSRC, 'bnministem.h'), os.path.join(CSRC, 'step_control.h'), os.path.join(CSRC, 'host_common.h'), os.path.join(CSRC, 'butcher.h'),
+HEADERS = [os.path.join(CSRC, 'node_internal.h'), os.path.join(CSRC, 'wino4.h'), os.path.join(CSRC, 'w4_gemm.h'), os.path.join(CSRC, 'theta_finalize.h'), os.path.join(CSRC, 'w4s_pass_body.inc'), os.path.join(CSRC, 'w4_gemm64h_body.inc'), os.path.join(CSRC, 'w4_wgrad64h_body.inc'), os.path.join(CSRC, 'conv_common.h'), os.path.join(CSRC, 'pointwise_common.h'), os.path.join(CSRC, 'stem.h'), os.path.join(CSRC, 'stem_split.h'), os.path.join(CSRC, 'batchnorm.h'), os.path.join(CSRC, 'bnfunc.h'), os.path.join(CSRC, 'attack.h'), os.path.join(CSRC, 'stem_plan.h'), os.path.join(CSRC, 'ministem.h'), os.path.join(CSRC, 'bnministem.h'), os.path.join(CSRC, 'step_control.h'), os.path.join(CSRC, 'host_common.h'), os.path.join(CSRC, 'butcher.h'),
            os.path.join(CSRC, 'plan.h'), os.path.join(CSRC, 'solver.h'), os.path.join(ROOT, 'include', 'node_hip.h')]
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 FLAGS = ['--offload-arch=gfx950', '-O3', '-fPIC', '-std=c++17', '-Wall', '-Wno-unused-function',

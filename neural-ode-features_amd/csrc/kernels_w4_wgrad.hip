@@ -1,5 +1,6 @@
 // Winograd F(4x4,3x3) pipeline: the weight gradients in the transform domain -- k_w4_wgrad (fp32 MFMA), k_w4_wgrad128b (bf16
-// triples, long filters), k_w4_wgrad64h (fp16 pairs).  gfx950 (MI355X / CDNA4) only.  See wino4.h for the data layouts.
+// triples, long filters), k_w4_wgrad64h (fp16 pairs) -- and k_w4_gemm64h_wgrad64h, the fp16-pair weight gradient and the conv-1 data
+// gradient's component GEMMs of an augmented evaluation as one launch.  gfx950 (MI355X / CDNA4) only.  See wino4.h for the data layouts.
 #include "w4_gemm.h"
 #include <cstring>
 
@@ -349,98 +350,9 @@ struct W4WgradHArgs {
 typedef short w4_s16x4 __attribute__((ext_vector_type(4)));
 typedef short w4_s16x8 __attribute__((ext_vector_type(8)));
 __global__ __launch_bounds__(256, 2) void k_w4_wgrad64h(W4WgradHArgs a) {
-  if (a.ctrl != nullptr && a.ctrl->done) return;
-  extern __shared__ __attribute__((aligned(16))) unsigned char wsm[];   // [W4WH_NST][V image 8 KB | Z image 8 KB]
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int C = a.C, nRB = a.N >> 3, G16 = C >> 4, nCT = C >> 7, T = nCT * nCT;
-  const int per_xcd = (36 * a.layers) >> 3;                       // (layer, component) pairs per XCD: 9 or 4.5 -> see the launcher
-  const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
-  const bool by_xcd = ((36 * a.layers) & 7) == 0;                 // (one layer -- the stem's: 36 pairs do not split over 8 XCDs: in order)
-  const int pair = by_xcd ? xcd * per_xcd + slot / T : (int)blockIdx.x / T, tile = by_xcd ? slot % T : (int)blockIdx.x % T;
-  const int layer = pair / 36, comp = pair - layer * 36;
-  const int cit = tile / nCT, cot = tile - cit * nCT;
-  const size_t cbytes = (size_t)nRB * G16 * 2048;                 // bytes per component
-  const unsigned char* Vb = reinterpret_cast<const unsigned char*>(a.V[layer]) + comp * cbytes;
-  const unsigned char* Zb = reinterpret_cast<const unsigned char*>(a.Z[layer]) + comp * cbytes;
-  const float inv = ldexpf(1.f, -(*a.v_exp[layer] + *a.z_exp));
-
-  // --- DMA roles: wave w brings instructions i = 4 w .. 4 w + 3 of a stage: i < 8 the V block g2l = i (lanes 0-31 part h, 32-63
-  // part l), else the Z block g2l = i - 8.  Lane -> its 16-B chunk of the 512-B half part: LDS slot (s', hi, t) <- source (s' ^ odd, hi, t)
-  const unsigned char* src[4];
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int i = 4 * wave + k, isz = i >> 3, g2l = i & 7;
-    const int part = lane >> 5, sg = lane & 31, ss = (sg >> 3) ^ (g2l & 1), hi = (sg >> 2) & 1, t = sg & 3;
-    const int g2 = (isz ? cot : cit) * 8 + g2l;
-    src[k] = (isz ? Zb : Vb) + ((size_t)g2 * 2 + part) * 1024 + ((ss * 2 + hi) * 4 + t) * 16;
-  }
-  const size_t rb_bytes = (size_t)G16 * 2048;
-  const unsigned lds0 = (unsigned)(size_t)(w4_lds_ptr_t)wsm + (unsigned)(4 * wave) * 1024u;
-  auto issue = [&](int q) {                                       // K step q = (row block q / 2, half q % 2)
-    const size_t off = (size_t)(q >> 1) * rb_bytes + (size_t)(q & 1) * 512;
-    const unsigned dst = lds0 + (unsigned)(q % W4WH_NST) * W4WH_STAGE;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) w4wh_dma(src[k] + off, dst + (unsigned)k * 1024u);
-  };
-  // --- fragment reads (ds_read_b64_tr_b16): lane = (kh, g2a, m = 4 q4 + p): rows = tiles q4 of samples 2 kh, 2 kh + 1; 8-byte column quad p
-  // = channels 4 p .. 4 p + 3 of its 16-channel block (hi = p & 1, gp = p >> 1); the lane receives channel m of the block
-  const int wr = wave >> 1, wc = wave & 1;
-  const int kh = lane >> 5, g2a = (lane >> 4) & 1, m = lane & 15, q4 = m >> 2, pq = m & 3;
-  const int lane_off = (pq & 1) * 64 + q4 * 16 + (pq >> 1) * 8;
-  const int s_lo = (2 * kh) ^ g2a, s_hi = (2 * kh + 1) ^ g2a;   // LDS slots of the two samples (odd blocks are stored swapped)
-  auto frag = [&](const unsigned char* img, int g2l0, int part) -> w4_f16x8 {
-    const unsigned char* pb = img + ((g2l0 + g2a) * 2 + part) * 512 + lane_off;
-    const w4_s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w4_s16x4*)(pb + s_lo * 128));
-    const w4_s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) w4_s16x4*)(pb + s_hi * 128));
-    const w4_s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(w4_f16x8, v);
-  };
-  float16_t acc[2][2];
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc[r][c][q] = 0.f;
-
-  const int nK = 2 * nRB;
-#pragma unroll
-  for (int q = 0; q < W4WH_D; ++q)
-    if (q < nK) issue(q);
-  for (int q = 0; q < nK; ++q) {
-    const int ahead = min(q + W4WH_D - 1, nK - 1) - q;          // stages issued behind stage q
-    if (ahead >= 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else if (ahead == 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // this wave's reads of stage q - 1 are in registers (its slot is refilled next)
-    __builtin_amdgcn_s_barrier();
-    if (q + W4WH_D < nK) issue(q + W4WH_D);
-    const unsigned char* st = wsm + (q % W4WH_NST) * W4WH_STAGE;
-    w4_f16x8 A[2][2], B[2][2];
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-      for (int part = 0; part < 2; ++part) {
-        A[r][part] = frag(st, 4 * wr + 2 * r, part);
-        B[r][part] = frag(st + 8192, 4 * wc + 2 * r, part);
-      }
-#define W4WH_P(AP, BQ)                                                                       \
-  _Pragma("unroll") for (int r = 0; r < 2; ++r) _Pragma("unroll") for (int c = 0; c < 2; ++c)  \
-      acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[r][AP], B[c][BQ], acc[r][c], 0, 0, 0);
-    W4WH_P(1, 0) W4WH_P(0, 1) W4WH_P(0, 0)   // smallest products first
-#undef W4WH_P
-  }
-  // accumulator register q of a lane: row (q & 3) + 8 (q >> 2) + 4 kh = channel ci of the block, column lane & 31 = co
-  float* o = a.dU + ((size_t)layer * 36 + comp) * C * C + (size_t)(cit * 128 + 64 * wr) * C + cot * 128 + 64 * wc + (lane & 31);
-#pragma unroll
-  for (int r = 0; r < 2; ++r)
-#pragma unroll
-    for (int c = 0; c < 2; ++c)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        const int row = (q & 3) + 8 * (q >> 2) + 4 * kh;
-        st_wt(o + (size_t)(32 * r + row) * C + 32 * c, acc[r][c][q] * inv);
-      }
+#define W4_BLOCK blockIdx.x
+#include "w4_wgrad64h_body.inc"
+#undef W4_BLOCK
 }
 bool w4_wgrad_f16_fits(int N, int C) {
   const W4Switches& sw = w4_switches();
@@ -457,6 +369,75 @@ void launch_w4_wgrad_f16(const unsigned* V1, const unsigned* Z1, const unsigned*
   const int T = (C >> 7) * (C >> 7);
   allow_full_lds(reinterpret_cast<const void*>(k_w4_wgrad64h), attr);
   hipLaunchKernelGGL(k_w4_wgrad64h, dim3(36 * a.layers * T), dim3(256), (size_t)W4WH_NST * W4WH_STAGE, s, a);
+}
+
+// ----------------------------------------------------------------------------
+// k_w4_gemm64h_wgrad64h: an augmented evaluation's weight gradient (k_w4_wgrad64h) and its conv-1 data gradient's component GEMMs
+// (k_w4_gemm64h) as ONE launch, a concatenated grid: the first `split` workgroups run one kernel's body, the rest the other's, each
+// on its own index W4_BLOCK = blockIdx.x minus its offset.  Both grids are multiples of 8, so a workgroup of either half keeps its
+// blockIdx & 7 -> XCD role and its work decomposition.  Neither half reads what the other writes (the weight gradient: V pairs, Z
+// pairs -> dU; the GEMM: W4V, U pairs -> M) and NOTHING waits across workgroups: the halves only share the chip, so that one half's
+// ring fill, store tail and kernel boundary are covered by the other half's streams.  Both bodies are 256 threads; each tests
+// ctrl->done in front of its first request and returns as a whole workgroup (no barrier is left behind a returning wave).  The bodies
+// are the stand-alone kernels' text (w4_gemm64h_body.inc, w4_wgrad64h_body.inc): same sums in the same order, same bits.
+// Registers: the launch is allocated for the larger half.  MINB = 1: the GEMM's own budget (one wave per SIMD, ring depth 4) -- the
+// weight gradient's workgroups then run ONE per CU instead of two; MINB = 2: at most 256 registers, two workgroups of either half
+// per CU, the GEMM's ring at depth D = 2 (two waves per SIMD keep as many requests in flight as one wave at depth 4).
+// profiles/wgrad_paired_ab.txt has the register counts and what was measured.
+// ----------------------------------------------------------------------------
+struct W4PairArgs {
+  const unsigned* Vh; const unsigned* Uh; float* M; const int* v_exp; const int* u_exp; W4Geom gm; int mode;   // the GEMM's
+  W4WgradHArgs w;                                                                                              // the weight gradient's
+  unsigned split; int wgrad_first;    // workgroups of the half that comes first in the grid / which half that is
+};
+template <int D, int MINB>
+__global__ __launch_bounds__(256, MINB) void k_w4_gemm64h_wgrad64h(W4PairArgs pa) {
+  const bool head = blockIdx.x < pa.split;
+  const unsigned block = head ? blockIdx.x : blockIdx.x - pa.split;
+#define W4_BLOCK block
+  if (head == (pa.wgrad_first == 0)) {
+    const unsigned* __restrict__ Vh = pa.Vh;
+    const unsigned* __restrict__ Uh = pa.Uh;
+    float* __restrict__ M = pa.M;
+    const Ctrl* ctrl = pa.w.ctrl;
+    const W4Geom gm = pa.gm;
+    const int mode = pa.mode;
+    const int* v_exp = pa.v_exp;
+    const int* u_exp = pa.u_exp;
+    unsigned long long* const stamps = nullptr;
+#include "w4_gemm64h_body.inc"
+  } else {
+    const W4WgradHArgs& a = pa.w;
+#include "w4_wgrad64h_body.inc"
+  }
+#undef W4_BLOCK
+}
+// variant (NODE_TUNE_WGRAD_PAIRED): bit 0 set; bit 1: the GEMM's workgroups first (default: the weight gradient's); bit 2: MINB = 1
+void launch_w4_pair_f16_64(const unsigned* Vh, const unsigned* Uh, float* M, const W4Geom& gm, int mode, const int* gv_exp, const int* gu_exp,
+                           const unsigned* V1, const unsigned* Z1, const unsigned* V2, const unsigned* Z2, float* dU, const Ctrl* ctrl,
+                           const int* v1_exp, const int* v2_exp, const int* z_exp, int variant, hipStream_t s) {
+  static bool attr[3][MAX_DEVICES] = {};
+  W4PairArgs pa;
+  memset(&pa, 0, sizeof(pa));
+  pa.Vh = Vh; pa.Uh = Uh; pa.M = M; pa.v_exp = gv_exp; pa.u_exp = gu_exp; pa.gm = gm; pa.mode = mode;
+  pa.w.V[0] = V1; pa.w.Z[0] = Z1; pa.w.V[1] = V2; pa.w.Z[1] = Z2; pa.w.dU = dU; pa.w.ctrl = ctrl; pa.w.N = gm.N; pa.w.C = gm.C;
+  pa.w.layers = 2;
+  pa.w.v_exp[0] = v1_exp; pa.w.v_exp[1] = v2_exp; pa.w.z_exp = z_exp;
+  const unsigned gemm_blocks = (gm.N / 16) * (gm.C >> 6) * 8, wgrad_blocks = 72 * (gm.C >> 7) * (gm.C >> 7);   // (the stand-alone launchers' grids)
+  pa.wgrad_first = (variant & 2) == 0;
+  pa.split = pa.wgrad_first ? wgrad_blocks : gemm_blocks;
+  const dim3 grid(gemm_blocks + wgrad_blocks);
+  const size_t lds = (size_t)W4WH_NST * W4WH_STAGE;      // the weight gradient's ring; the GEMM half uses the first 32 KB
+  if ((variant & 4) != 0 && (gm.C >> 4) % 4 == 0) {
+    allow_full_lds(reinterpret_cast<const void*>(k_w4_gemm64h_wgrad64h<4, 1>), attr[0]);
+    hipLaunchKernelGGL((k_w4_gemm64h_wgrad64h<4, 1>), grid, dim3(256), lds, s, pa);
+  } else if ((variant & 4) != 0) {
+    allow_full_lds(reinterpret_cast<const void*>(k_w4_gemm64h_wgrad64h<2, 1>), attr[1]);
+    hipLaunchKernelGGL((k_w4_gemm64h_wgrad64h<2, 1>), grid, dim3(256), lds, s, pa);
+  } else {
+    allow_full_lds(reinterpret_cast<const void*>(k_w4_gemm64h_wgrad64h<2, 2>), attr[2]);
+    hipLaunchKernelGGL((k_w4_gemm64h_wgrad64h<2, 2>), grid, dim3(256), lds, s, pa);
+  }
 }
 
 void launch_w4_wgrad(const W4WgradArgs& a_in, hipStream_t s) {

@@ -109,7 +109,12 @@ struct Solver {
   // P3B3(i+1) (gpart[2], spart[1]), PB2(i+1) (gpart[1], spart[0]), the weight gradient (W4dU / wpart) and PB1(i+1) (gpart[0]):
   // all of them behind the kernel boundary after P2(i+1).  What it writes -- KT[k], and ctrl->ts_k[k] from its last workgroup --
   // nothing reads before the step's k_error_norm / k_step_controller; P2 reads ctrl->done, t, dt (h0), other words of the record.
-  // A waiting finalize never survives the end of enqueue_step. ----
+  // A waiting finalize never survives the end of enqueue_step.
+  // Re-checked with the paired launch (NODE_TUNE_WGRAD_PAIRED, k_w4_gemm64h_wgrad64h: the weight gradient and the conv-1 data
+  // gradient's GEMM of evaluation i + 1 in one launch, W4dU written concurrently with W4M): the launch sits where the two sat, behind
+  // PB2(i+1) and so behind P2(i+1), which carried the finalize.  Inside it the GEMM half reads W4V (PB2's) and the packed filters,
+  // the weight-gradient half va0, W4Va[1], W4Z[0..1]: neither reads W4M or W4dU.  The first readers are PB1(i+1) (W4M) and the
+  // finalize of evaluation i + 1 (W4dU: its own launch behind PB1, or the rider of P2(i+2)) -- both behind the launch's end. ----
   bool theta_rider = true;          // NODE_TUNE_THETA_RIDER (default 1; 0: every finalize is its own launch), read in prepare()
   bool tf_waiting = false;
   ThetaFinalizeArgs tf_wait;

@@ -362,7 +362,16 @@ int Solver::eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_
     if (f16_now()) { a.v_exp = &p.w4sc->e[W4_E_G]; a.z_exp = &p.w4sc->e[W4_E_G]; }
     w4_pass(2, 0, a);
   }
-  if (need_theta && wg4 && f16_now()) {
+  // the weight gradient and the conv-1 data gradient's GEMM are independent (solver.h): one launch where the batch has the kernel
+  const bool paired = need_theta && wg4 && f16_now() && w4_pair_fits(d.N8, d.C);
+  if (paired) {
+    // profile class 1 with the FLOPs of both halves: the GEMM's share is not in class 2 ("paired launch")
+    ProfScope ps(1, 3.0 * conv_flops(), st);
+    launch_w4_gemm_wgrad_f16(reinterpret_cast<const unsigned*>(p.W4V), reinterpret_cast<const unsigned*>(p.w4u[2]), p.W4M, &p.w4sc->e[W4_E_G],
+                             &p.w4sc->e[W4_E_U1], reinterpret_cast<const unsigned*>(va0_of(cur)), reinterpret_cast<const unsigned*>(p.W4Z[0]),
+                             reinterpret_cast<const unsigned*>(p.W4Va[1]), reinterpret_cast<const unsigned*>(p.W4Z[1]), p.W4dU, p.ctrl, d.N8, d.C,
+                             &p.w4sc->e[W4_E_V1], &p.w4sc->e[W4_E_V2], &p.w4sc->e[W4_E_G], st);
+  } else if (need_theta && wg4 && f16_now()) {
     ProfScope ps(1, 2.0 * conv_flops(), st);
     launch_w4_wgrad_f16(reinterpret_cast<const unsigned*>(va0_of(cur)), reinterpret_cast<const unsigned*>(p.W4Z[0]), reinterpret_cast<const unsigned*>(p.W4Va[1]),
                         reinterpret_cast<const unsigned*>(p.W4Z[1]), p.W4dU, p.ctrl, d.N8, d.C, &p.w4sc->e[W4_E_V1], &p.w4sc->e[W4_E_V2], &p.w4sc->e[W4_E_G], st);
@@ -384,7 +393,7 @@ int Solver::eval_w4(const Comb& cy, float* y_out, const EvalTime& et, float* kY_
       { ProfScope ps(1, conv_flops(), st); launch_wgrad(d, w2, st); }
     }
   }
-  w4_gemm(2);   // data gradient of conv1
+  if (!paired) w4_gemm(2);   // data gradient of conv1
   {   // PB1 (+ the next evaluation's combine)
     W4sArgs a = w4_args();
     a.h.M = p.W4M; a.h.gamma = prm.norm1_w; a.h.beta = prm.norm1_b; a.h.xhat_s = xh1_of(cur); a.h.rstd = r1_of(cur);

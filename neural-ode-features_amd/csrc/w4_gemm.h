@@ -3,7 +3,7 @@
 //   kernels_w4_f32.hip     fp32 MFMA:    k_w4_gemm, k_w4_gemm64, k_w4_gemm_small
 //   kernels_w4_bf16.hip    bf16 triples: k_w4_gemm64b, k_w4_gemm128b
 //   kernels_w4_f16.hip     fp16 pairs:   k_w4_gemm64h, k_w4_gemm128h, k_w4_gemm256h
-//   kernels_w4_wgrad.hip   the weight gradients of all three families
+//   kernels_w4_wgrad.hip   the weight gradients of all three families; k_w4_gemm64h_wgrad64h (weight gradient + one GEMM, one launch)
 //   w4_select.hip          the NODE_TUNE_W4_* switches, which kernel runs for (N, C), launch_w4_gemm / launch_w4_gemm_f16
 //   kernels_w4_diag.hip    measured-and-rejected variants: libnode_hip_diag.so only (build.py --diag)
 // A kernel is launched from the file that defines it: every family exports plain host launchers (below) and w4_select.hip
@@ -200,7 +200,69 @@ __device__ __forceinline__ void w4c_mac(float16_t (&acc)[2][2], const w4_u32x4 (
 }
 
 // ----------------------------------------------------------------------------
-// The A/B switches that select the component-GEMM kernel (w4_select.hip).  ONE reader for the packer (which filter forms a
+// The register ring of the fp16-pair kernels that read their operands straight from L2 (k_w4_gemm64h, the shared piece of
+// k_w4_gemm128h, and the GEMM half of k_w4_gemm64h_wgrad64h in kernels_w4_wgrad.hip): both operands arrive as MFMA fragments.
+// ----------------------------------------------------------------------------
+struct W4HStage { w4_u32x4 a[2][2], b[2][2]; };    // [row block][part h, l], [column block][part]
+struct W4HCursor { const w4_u32x4* a[2]; const w4_u32x4* b[2]; };
+template <int NRB>
+__device__ __forceinline__ void w4h_next(W4HStage& s, W4HCursor& cu) {   // the next K = 16 step of the streams (2 KB per stream and step)
+#pragma unroll
+  for (int r = 0; r < NRB; ++r) {
+    s.a[r][0] = cu.a[r][0];
+    s.a[r][1] = cu.a[r][64];
+    cu.a[r] += 128;
+  }
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {
+    s.b[c][0] = cu.b[c][0];
+    s.b[c][1] = cu.b[c][64];
+    cu.b[c] += 128;
+  }
+}
+template <int NRB>
+__device__ __forceinline__ void w4h_mac(float16_t (&acc)[2][2], const W4HStage& s) {
+  w4_f16x8 A[2][2], B[2][2];
+#pragma unroll
+  for (int r = 0; r < NRB; ++r)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) A[r][q] = __builtin_bit_cast(w4_f16x8, s.a[r][q]);
+#pragma unroll
+  for (int c = 0; c < 2; ++c)
+#pragma unroll
+    for (int q = 0; q < 2; ++q) B[c][q] = __builtin_bit_cast(w4_f16x8, s.b[c][q]);
+#define W4H_P(AP, BQ)                                                                             \
+  _Pragma("unroll") for (int r = 0; r < NRB; ++r) _Pragma("unroll") for (int c = 0; c < 2; ++c)   \
+      acc[r][c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A[r][AP], B[c][BQ], acc[r][c], 0, 0, 0);
+  W4H_P(1, 0) W4H_P(0, 1) W4H_P(0, 0)   // smallest products first
+#undef W4H_P
+}
+// acc += sum over K = 16 steps [g0, g0 + n) (n a multiple of D): a ring of D stages, each refilled right behind the MFMAs that
+// consumed it (the refills of the last D steps read up to D steps past the range: buffer slack)
+template <int D, int NRB, class F = W4Nothing>
+__device__ __forceinline__ void w4h_run(float16_t (&acc)[2][2], const W4HCursor& start, int n, F after_fill = F(), unsigned long long* st = nullptr) {
+  W4HStage ring[D];
+  W4HCursor cu = start;
+#pragma unroll
+  for (int i = 0; i < D; ++i) {
+    w4h_next<NRB>(ring[i], cu);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  after_fill();
+  w4_stamp(st, 1);
+  for (int g = 0; g < n; g += D) {
+    if (g == D) w4_stamp(st, 2);
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+      w4h_mac<NRB>(acc, ring[i]);
+      __builtin_amdgcn_sched_barrier(0);   // the refill stays behind the MFMAs that read the old contents
+      w4h_next<NRB>(ring[i], cu);
+    }
+  }
+}
+
+// ----------------------------------------------------------------------------
+// The A/B switches that select the component-GEMM kernel (w4_select.hip). ONE reader for the packer (which filter forms a
 // solve prepares) and the launchers (which kernel reads them): a process that changes a switch between solves (the tests do)
 // can never pack for one kernel and launch another.  Under every setting the results stay correct: the switches choose which
 // kernel family multiplies and how a component's tiles are dealt to waves (bit-identical).
@@ -210,9 +272,14 @@ __device__ __forceinline__ void w4c_mac(float16_t (&acc)[2][2], const w4_u32x4 (
 //   NODE_TUNE_W4_GEMM128 / _WGRAD128 = 0 never / 1 wherever it fits / unset (-1): long reductions (C >= 512)
 //   NODE_TUNE_W4_H256 = 0 never / 1 where whole rounds of the chip are filled / 2 wherever the geometry has the tiles (tests)
 //   NODE_TUNE_W4_SHAREV = 1 / 2  how k_w4_gemm64b / k_w4_gemm64h / k_w4_wgrad deal a component's tiles to the waves of a workgroup
+//   NODE_TUNE_WGRAD_PAIRED = 0   an augmented evaluation's fp16-pair weight gradient and conv-1 data gradient as two launches;
+//                            1   (default) as ONE launch (k_w4_gemm64h_wgrad64h) where w4_pair_fits, the weight gradient's workgroups
+//                                first in the grid, 256 registers (two workgroups of either half per CU);
+//                            3 / 5 / 7  measured variants: + 2 the GEMM's workgroups first, + 4 the GEMM's own register budget
 // ----------------------------------------------------------------------------
 struct W4Switches {
   int g64, b16, sharev, gemm128, wgrad128, f16, h256;
+  int wgrad_paired;              // NODE_TUNE_WGRAD_PAIRED (below)
   // libnode_hip_diag.so only (0 / null in the product library):
   int early;                     // NODE_TUNE_W4_EARLY: k_w4_gemm64b's mode bit 3
   unsigned long long* stamps;    // NODE_TUNE_W4_STAMPS = device address of [grid * 4][16] u64 (tools/w4_stamps.py)
@@ -245,6 +312,10 @@ void launch_w4_gemm_bf16_64(const float* V, const unsigned short* Ub, float* M, 
 void launch_w4_gemm_bf16_128(const float* V, const unsigned short* Ub, float* M, const Ctrl* ctrl, const W4Geom& gm, hipStream_t s);
 void launch_w4_gemm_f16_64(const unsigned* Vh, const unsigned* Uh, float* M, const Ctrl* ctrl, const W4Geom& gm, int mode, const int* v_exp,
                            const int* u_exp, unsigned long long* stamps, hipStream_t s);
+// k_w4_gemm64h_wgrad64h (kernels_w4_wgrad.hip): launch_w4_gemm_f16_64 and launch_w4_wgrad_f16 (two layers) as one launch
+void launch_w4_pair_f16_64(const unsigned* Vh, const unsigned* Uh, float* M, const W4Geom& gm, int mode, const int* gv_exp, const int* gu_exp,
+                           const unsigned* V1, const unsigned* Z1, const unsigned* V2, const unsigned* Z2, float* dU, const Ctrl* ctrl,
+                           const int* v1_exp, const int* v2_exp, const int* z_exp, int variant, hipStream_t s);
 // tail: components 32..35 only (behind launch_w4_gemm_f16_256, which leaves them out)
 void launch_w4_gemm_f16_128(const unsigned* Vh, const unsigned* Uh, float* M, const Ctrl* ctrl, const W4Geom& gm, const int* v_exp,
                             const int* u_exp, bool tail, hipStream_t s);

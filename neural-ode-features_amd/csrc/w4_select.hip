@@ -23,7 +23,7 @@ static bool launch_w4_gemm_variant(const W4Switches&, const float*, const unsign
 static W4Switches w4_read_switches() {
   auto rd = env_int;
   W4Switches sw = {rd("NODE_TUNE_W4_GEMM64", 1), rd("NODE_TUNE_W4_BF16X3", 1), rd("NODE_TUNE_W4_SHAREV", 1), rd("NODE_TUNE_W4_GEMM128", -1),
-                   rd("NODE_TUNE_W4_WGRAD128", -1), rd("NODE_TUNE_W4_F16", 1), rd("NODE_TUNE_W4_H256", 1), 0, nullptr};
+                   rd("NODE_TUNE_W4_WGRAD128", -1), rd("NODE_TUNE_W4_F16", 1), rd("NODE_TUNE_W4_H256", 1), rd("NODE_TUNE_WGRAD_PAIRED", 1), 0, nullptr};
   w4_diag_switches(sw);
   return sw;
 }
@@ -119,6 +119,21 @@ void launch_w4_gemm_f16(const unsigned* Vh, const unsigned* Uh, float* M, const 
       fprintf(stderr, "launch_w4_gemm_f16: no fp16-pair kernel for N = %d, C = %d\n", N, C);
       abort();
   }
+}
+
+// The pair of an augmented evaluation -- weight gradient and conv-1 data gradient -- as one launch: where the GEMM is k_w4_gemm64h
+// (C < 512) and the weight gradient k_w4_wgrad64h.  Every other batch keeps the two launches.
+bool w4_pair_fits(int N, int C) {
+  const W4Switches& sw = w4_switches();
+  return (sw.wgrad_paired & 1) != 0 && sw.f16 != 0 && w4_select_gemm(sw, N, C, W4Operands::Pairs) == W4Gemm::F16_64 &&
+         w4_select_wgrad(sw, N, C, true, W4Operands::Pairs) == W4Wgrad::F16_64;
+}
+void launch_w4_gemm_wgrad_f16(const unsigned* Vh, const unsigned* Uh, float* M, const int* gv_exp, const int* gu_exp, const unsigned* V1,
+                              const unsigned* Z1, const unsigned* V2, const unsigned* Z2, float* dU, const Ctrl* ctrl, int N, int C,
+                              const int* v1_exp, const int* v2_exp, const int* z_exp, hipStream_t s) {
+  const W4Switches& sw = w4_switches();
+  launch_w4_pair_f16_64(Vh, Uh, M, w4_geom(N, C), w4_sharev_mode(sw), gv_exp, gu_exp, V1, Z1, V2, Z2, dU, ctrl, v1_exp, v2_exp, z_exp,
+                        sw.wgrad_paired, s);
 }
 
 }  // namespace node

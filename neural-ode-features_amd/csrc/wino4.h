@@ -220,6 +220,12 @@ void launch_w4_wgrad(const W4WgradArgs& a, hipStream_t s);
 bool w4_wgrad_f16_fits(int N, int C);
 void launch_w4_wgrad_f16(const unsigned* V1, const unsigned* Z1, const unsigned* V2, const unsigned* Z2, float* dU, const Ctrl* ctrl, int N, int C,
                          const int* v1_exp, const int* v2_exp, const int* z_exp, hipStream_t s);
+// launch_w4_gemm_f16 (Vh, Uh -> M at gv_exp / gu_exp) and launch_w4_wgrad_f16 (-> dU) in ONE launch (k_w4_gemm64h_wgrad64h): neither
+// reads what the other writes; nothing may read M or dU before the launch ends.  Only where w4_pair_fits (NODE_TUNE_WGRAD_PAIRED).
+bool w4_pair_fits(int N, int C);
+void launch_w4_gemm_wgrad_f16(const unsigned* Vh, const unsigned* Uh, float* M, const int* gv_exp, const int* gu_exp, const unsigned* V1,
+                              const unsigned* Z1, const unsigned* V2, const unsigned* Z2, float* dU, const Ctrl* ctrl, int N, int C,
+                              const int* v1_exp, const int* v2_exp, const int* z_exp, hipStream_t s);
 void w4_refresh_tuning();     // re-read the NODE_TUNE_W4_* switches (once per C-ABI call; w4_select.hip)
 __host__ __device__ inline size_t w4_z_elems(int N, int C) { return (size_t)W4_COMPS * 4 * N * C; }
 __host__ __device__ inline size_t w4_du_elems(int C) { return (size_t)2 * W4_COMPS * C * C; }
